@@ -8,19 +8,21 @@ synthetic 64x64 tiles per GPU, inputs resident in HBM, random-init weights of th
 A "step" is one forward_feature over one batch.  Tiles are independent, so ranks shard the tile stream with
 no data-path collective ("scaling": "weak"); the only collectives are the timing barrier / max.
 
-One JSON line is printed by rank 0 (contract in the task statement).  Extra keys of the default run:
+One JSON line is printed by rank 0.  A plain run sets up, warms up, times K steps and
+prints the headline (`value`, `ms_per_step`, ...); `--dump-outputs DIR` also writes the last timed step's output to DIR
+(dump_feature_outputs).  `--full` adds these keys to the default run:
   roofline     -- MFMA roofline of the dominant kernel (persistent trunk), launch duration measured live with HIP events
                   on the launch stream; `traffic` is the PMC figure RECORDED under profiles/ (`traffic_source` says so).
   cpu_baseline -- the CPU oracle (oracle/srbh_oracle.py, proven equal to the reference) timed on this host (N=1 only).
   train_step   -- BASELINE configs[2] (N=1) / configs[3] (N>1): the full training step at batch 64 per GPU, a few timed
                   steps, with per-kernel rooflines of its dominant kernels (trunk: MFMA; head convs: HBM), the gradient
                   all-reduce's isolated and exposed time (N>1) and a CPU baseline at B=4 (N=1).
-  predict      -- BASELINE configs[4]: tiled city inference incl. quantise + integer mosaic, the FIRST 30 of the 301 synthetic
-                  cities (an unbiased draw of the stated size distribution: 3 cities > 10 k cells, every ragged-tail shape),
+  predict      -- BASELINE configs[4]: tiled city inference incl. quantise + integer mosaic, all 301 synthetic cities
+                  (an unbiased draw of the stated size distribution: 3 cities > 10 k cells, every ragged-tail shape),
                   tiles/s and p50 per-city latency.
   parity       -- the headline output on one tile against the strict-fp32 GPU path and (N=1) the CPU oracle: rel-L2, RMSE.
-`--workload train|predict|epoch` run one of those as the headline instead (longer, all cities / a whole epoch).
-`--no-extras` drops the two sub-objects from the default run.
+`--workload train|predict|epoch|sr_train` run one of those as the headline instead (longer, all cities / a whole epoch).
+`--no-extras` drops the two sub-objects (and the parity sweep) from a `--full` run.
 """
 import argparse
 import glob
@@ -678,6 +680,22 @@ def _sr_trunk_kernels(net, batch, dev, num_block, reps=10):
     return rows
 
 
+DUMP_SAMPLE = 1 << 22      # elements of the seeded sample of the whole batch's output (16 MB as float32)
+
+
+def dump_feature_outputs(y, outdir):
+    """--dump-outputs: what the last timed forward_feature returned, as float32 .npy files (32 MB in all).
+    feature_tile0.npy = the first tile's features (64, 256, 256), NCHW; feature_sample.npy = DUMP_SAMPLE elements of the whole
+    (B, 64, 256, 256) output taken in NCHW order at indices drawn from a fixed seed (sorted), the same for every run of the same shape."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    y = y.detach().float()
+    np.save(os.path.join(outdir, "feature_tile0.npy"), y[0].contiguous().cpu().numpy())
+    flat = y.contiguous().view(-1)
+    idx = torch.randint(0, flat.numel(), (min(DUMP_SAMPLE, flat.numel()),), generator=torch.Generator().manual_seed(2024))
+    np.save(os.path.join(outdir, "feature_sample.npy"), flat[idx.sort().values.to(flat.device)].cpu().numpy())
+
+
 def _sr_paths():
     from srbh_amd import rrdbnet_autograd as RA
     return RA.TRUNK_FWD_PATHS, RA.TRUNK_BWD_PATHS
@@ -723,7 +741,28 @@ def bench_feature(args, rank, world, dev, dist):
     elapsed, gpu_ms = _max_over_ranks([elapsed, gpu_ms], dev, dist)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_feature_outputs(y, args.dump_outputs)
     tiles = B * args.steps * world
+    strict = bool(net._use_strict())          # SRBH_TRUNK_PRECISION=f32 / net.precision: exact-fp32 matrix cores, one launch per conv
+    if strict:
+        dtype = "f32 operands / f32 accumulate (v_mfma_f32_16x16x4_f32, one launch per conv), f32 residual stream"
+        peak = PEAK_F32_MFMA_TFLOPS
+    else:
+        dtype = "f16 operands / f32 accumulate (MFMA), f32 residual stream"
+        peak = PEAK_F16_TFLOPS
+    line = {
+        "metric": "tiles/sec (64x64x8ch->256x256 height)", "value": round(tiles / elapsed, 2), "unit": "tiles/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": dtype,
+        "data": "synthetic uniform[0,1) tiles, random-init weights (no datasets/checkpoints offline)",
+        "config": {"workload": f"RRDBNet x4 ({args.num_block} RRDB, 64 feat) forward_feature, batch {B} tiles/GPU, "
+                               "64x64x3 -> 64x256x256 (BASELINE.json configs[1])",
+                   "global_batch": B * world, "parallelism": f"tile-sharded x{world} (no data-path collective)"},
+    }
+    if not args.full:
+        return line
     step_s_events = gpu_ms / 1e3 / args.steps
     achieved = GFLOP_PER_TILE_FEATURE * (args.num_block * 5.8886 + 11.19) / 146.630 if args.num_block != 23 \
         else GFLOP_PER_TILE_FEATURE
@@ -736,7 +775,6 @@ def bench_feature(args, rank, world, dev, dist):
     L = _lib.lib()
     trunk_gflop_tile = args.num_block * 3 * 4096 * 18 * (64 * 32 + 96 * 32 + 128 * 32 + 160 * 32 + 192 * 64) / 1e9
     trunk_ms = None
-    strict = bool(net._use_strict())          # SRBH_TRUNK_PRECISION=f32 / net.precision: exact-fp32 matrix cores, one launch per conv
     if not strict and L.srbh_trunk_timing(1) == 0:
         acc, nrep = 0.0, max(5, min(20, args.steps))
         try:
@@ -758,37 +796,23 @@ def bench_feature(args, rank, world, dev, dist):
     traffic, traffic_src = (None, None)
     if B == 32 and args.num_block == 23 and not strict and trunk_ms:
         traffic, traffic_src = _recorded_traffic(kname)
-    if strict:
-        dtype = "f32 operands / f32 accumulate (v_mfma_f32_16x16x4_f32, one launch per conv), f32 residual stream"
-        peak = PEAK_F32_MFMA_TFLOPS
-    else:
-        dtype = "f16 operands / f32 accumulate (MFMA), f32 residual stream"
-        peak = PEAK_F16_TFLOPS
-    line = {
-        "metric": "tiles/sec (64x64x8ch->256x256 height)", "value": round(tiles / elapsed, 2), "unit": "tiles/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": dtype,
-        "data": "synthetic uniform[0,1) tiles, random-init weights (no datasets/checkpoints offline)",
-        "config": {"workload": f"RRDBNet x4 ({args.num_block} RRDB, 64 feat) forward_feature, batch {B} tiles/GPU, "
-                               "64x64x3 -> 64x256x256 (BASELINE.json configs[1])",
-                   "global_batch": B * world, "parallelism": f"tile-sharded x{world} (no data-path collective)"},
-        "roofline": {"bound": "mfma", "achieved": round(trunk_tflops, 2) if trunk_tflops else None, "peak": peak,
-                     "unit": "TFLOP/s", "frac": round(trunk_tflops / peak, 4) if trunk_tflops else None,
-                     "traffic": traffic,
-                     "traffic_source": ((f"{traffic_src} (RECORDED: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
-                                         "command, FETCH doubled per the guide; not measured in this run)") if traffic is not None else traffic_src),
-                     "power_capped_peak": None if strict else {
-                         "what": "tools/mfma_ceiling.hip on this package (RECORDED at this round's HEAD, profiles/r06d_mfma_ceiling.txt + r06d_mfma_ceiling_smi_summary.txt; package at 1 372 W of 1 400 W under the trunk itself, profiles/r06c_trunk_power_probe.txt): v_mfma_f32_32x32x16_f16 back to back, one wave "
-                                 "per SIMD, 256 CUs, real trunk operands, seconds-long runs: MFMA only / + the trunk's LDS read mix / + its weight LDS-DMA stream",
-                         "tflops": [1680.7, 1591.6, 1545.0], "frac_of_2500": [0.672, 0.637, 0.618], "sclk_mhz": [1653, 1582, 1586],
-                         "frac_of_measured_ceiling": round(trunk_tflops / 1545.0, 4) if trunk_tflops else None},
-                     "kernel": ("hconv_f32_kernel per conv (strict fp32: no single dominant kernel; see whole_forward)" if strict else
-                                f"{kname} (persistent trunk: 345 dense-block 3x3 convs in one launch)"),
-                     "avg_launch_ms": round(trunk_ms, 4) if trunk_ms else None,
-                     "algorithmic_gflop_per_launch": round(trunk_gflop_tile * B, 1),
-                     "whole_forward": {"achieved": round(tflops, 2), "frac": round(tflops / peak, 4),
-                                       "gflop": round(achieved * B, 1), "ms": round(step_s_events * 1e3, 4)}},
+    line["roofline"] = {
+        "bound": "mfma", "achieved": round(trunk_tflops, 2) if trunk_tflops else None, "peak": peak,
+        "unit": "TFLOP/s", "frac": round(trunk_tflops / peak, 4) if trunk_tflops else None,
+        "traffic": traffic,
+        "traffic_source": ((f"{traffic_src} (RECORDED: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
+                            "command, FETCH doubled for gfx950's 64 B tally per 128 B request; not measured in this run)") if traffic is not None else traffic_src),
+        "power_capped_peak": None if strict else {
+            "what": "tools/mfma_ceiling.hip on this package (RECORDED at this round's HEAD, profiles/r06d_mfma_ceiling.txt + r06d_mfma_ceiling_smi_summary.txt; package at 1 372 W of 1 400 W under the trunk itself, profiles/r06c_trunk_power_probe.txt): v_mfma_f32_32x32x16_f16 back to back, one wave "
+                    "per SIMD, 256 CUs, real trunk operands, seconds-long runs: MFMA only / + the trunk's LDS read mix / + its weight LDS-DMA stream",
+            "tflops": [1680.7, 1591.6, 1545.0], "frac_of_2500": [0.672, 0.637, 0.618], "sclk_mhz": [1653, 1582, 1586],
+            "frac_of_measured_ceiling": round(trunk_tflops / 1545.0, 4) if trunk_tflops else None},
+        "kernel": ("hconv_f32_kernel per conv (strict fp32: no single dominant kernel; see whole_forward)" if strict else
+                   f"{kname} (persistent trunk: 345 dense-block 3x3 convs in one launch)"),
+        "avg_launch_ms": round(trunk_ms, 4) if trunk_ms else None,
+        "algorithmic_gflop_per_launch": round(trunk_gflop_tile * B, 1),
+        "whole_forward": {"achieved": round(tflops, 2), "frac": round(tflops / peak, 4),
+                          "gflop": round(achieved * B, 1), "ms": round(step_s_events * 1e3, 4)},
     }
     # strict-fp32 GPU path (exact-fp32 matrix cores, one launch per conv) on ONE tile of the sample the CPU leg uses: the on-device
     # yardstick of the fp16-operand fast path; the CPU oracle's output for the same tile comes out of the cpu_baseline leg
@@ -869,8 +893,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=32, help="tiles per GPU per step (configs[1]: 32)")
     ap.add_argument("--num-block", type=int, default=23)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="default run: skip the train_step / predict sub-objects")
+    ap.add_argument("--full", action="store_true",
+                    help="default workload: also the trunk roofline, the parity checks, the CPU baseline and the train_step / predict "
+                         "sub-objects (without it the run times the steps and prints the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="default workload: write the last timed step's output to DIR as float32 .npy files (dump_feature_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline (default workload with --full, --workload train)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="default workload with --full: skip the parity sweep and the train_step / predict sub-objects; "
+                         "--workload train: skip the per-kernel rows, the strict-fp32 head, the gradient parity and the CPU baseline")
     ap.add_argument("--epoch-tiles", type=int, default=31500,
                     help="--workload epoch: tiles of the pass (default 31 500 = 45 000 x 0.7, data/datalist_globe_train_0.7.csv); drop_last")
     ap.add_argument("--details", default=None,
@@ -880,6 +911,10 @@ def main():
                          "configs[2]: full training step, batch 64; epoch = configs[3]: one DP pass over 31 500 synthetic tiles; "
                          "predict = configs[4]: tiled city inference incl. mosaic, one city per step (try --steps 12)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and args.workload != "feature":
+        ap.error("--dump-outputs is implemented for the default workload (feature) only")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -942,7 +977,7 @@ def main():
         line = bench_sr_train(args, rank, world, dev, dist, args.steps, args.warmup, batch=args.batch if args.batch != 32 else 8)
     else:
         line = bench_feature(args, rank, world, dev, dist)
-        if not args.no_extras and args.num_block == 23 and args.batch == 32:
+        if args.full and not args.no_extras and args.num_block == 23 and args.batch == 32:
             extras = {}
             for key, fn in (("train_step", lambda: bench_train(args, rank, world, dev, dist, 20, 8, batch=64,      # (8 warm-up + 20 timed steps: the pipelined step needs a few steps to settle; 5 + 10 read 1.8 ms above the 40-step figure)
                                                                 with_cpu=not args.no_cpu_baseline)),

@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 OUT=gpurun_out/ic
 mkdir -p $OUT
-timeout 300 rocprofv3 --kernel-trace --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQC_TC_INST_REQ SQ_IFETCH SQ_IFETCH_LEVEL SQ_WAVE_CYCLES --output-format csv -d $OUT/p1 -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline > $OUT/p1.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQC_TC_INST_REQ SQ_IFETCH SQ_IFETCH_LEVEL SQ_WAVE_CYCLES --output-format csv -d $OUT/p1 -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $OUT/p1.log 2>&1
 echo "rc=$?"
 python - <<'PY'
 import csv, glob, collections

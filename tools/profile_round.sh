@@ -13,7 +13,7 @@ mkdir -p $O
 FAILED=""
 bench_leg() {   # bench_leg <output log> <bench.py args...>
     local out=$1; shift
-    timeout 900 python bench.py "$@" > "$out" 2> "$out.err"
+    timeout 900 python bench.py --full "$@" > "$out" 2> "$out.err"
     local rc=$?
     if [ $rc -ne 0 ] || ! tail -1 "$out" | python -c "import sys, json; json.loads(sys.stdin.read())" 2> /dev/null; then
         echo "!! FAILED LEG (rc=$rc): bench.py $*"; tail -15 "$out.err"
@@ -35,12 +35,12 @@ bench_leg $O/${TAG}_bench_epoch.json.log --workload epoch
 SRBH_TRUNK_PRECISION=f32 bench_leg $O/${TAG}_bench_feature_b32_strict_f32_trunk.json.log --steps 3 --warmup 1 --no-extras --no-cpu-baseline
 bench_leg $O/${TAG}_bench_sr_train_b8.json.log --workload sr_train --steps 6 --warmup 2
 SRBH_SR_BENCH_MODES=fast,mixed bench_leg $O/${TAG}_bench_sr_train_b24.json.log --workload sr_train --steps 6 --warmup 2 --batch 24
-leg 'timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_stats -- python bench.py --no-cpu-baseline --no-extras > $O/${TAG}_stats.log 2>&1'
+leg 'timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_stats -- python bench.py --full --no-cpu-baseline --no-extras > $O/${TAG}_stats.log 2>&1'
 leg 'cp $(find $O/${TAG}_stats -name "*kernel_stats.csv" | head -1) $O/${TAG}_bench_feature_b32_kernel_stats.csv'
 # (the stats CSV averages EVERY launch of a kernel, the one-tile parity forwards included: the batch-32 launches on their own)
 leg 'python tools/trunk_launch_stats.py $O/${TAG}_stats > $O/${TAG}_trunk_launches_by_grid.txt'
-leg 'timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/${TAG}_pmc_fetch -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras > $O/${TAG}_pmc_fetch.log 2>&1'
-leg 'timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/${TAG}_pmc_write -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras > $O/${TAG}_pmc_write.log 2>&1'
+leg 'timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/${TAG}_pmc_fetch -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras > $O/${TAG}_pmc_fetch.log 2>&1'
+leg 'timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/${TAG}_pmc_write -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras > $O/${TAG}_pmc_write.log 2>&1'
 leg 'python tools/pmc_traffic.py $O/${TAG}_pmc_fetch $O/${TAG}_pmc_write $O/${TAG}_pmc_hbm_traffic.json'
 if [ "$MODE" != "quick" ]; then
 leg 'timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/${TAG}_tr -- python bench.py --workload train --steps 6 --warmup 3 --no-extras > /dev/null 2>&1'

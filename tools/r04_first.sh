@@ -7,4 +7,4 @@ timeout 1500 python -m pytest -x -q -m gpu tests/test_gpu_epoch.py tests/test_gp
     "tests/test_gpu_mbconv.py::test_bn_act_train_large_channel_offset" tests/test_gpu_mbconv.py::test_bn_act_train_matches_stock_ops 2>&1 | tail -15
 timeout 600 python bench.py --workload epoch > $O/r04a_bench_epoch.json.log 2> $O/r04a_bench_epoch.err; echo "epoch rc=$?"; tail -c 1500 $O/r04a_bench_epoch.json.log
 timeout 900 python tools/convergence_ab.py --steps 300 --batch 64 --out $O/r04a_convergence_ab.json > $O/r04a_convergence_ab.summary.json 2> $O/r04a_convergence_ab.err; echo "ab rc=$?"; cat $O/r04a_convergence_ab.summary.json
-timeout 900 python bench.py --details $O/r04a_bench_details.json > $O/r04a_bench_default.json.log 2> $O/r04a_bench_default.err; echo "default rc=$?"; wc -c $O/r04a_bench_default.json.log; tail -c 2500 $O/r04a_bench_default.json.log
+timeout 900 python bench.py --full --details $O/r04a_bench_details.json > $O/r04a_bench_default.json.log 2> $O/r04a_bench_default.err; echo "default rc=$?"; wc -c $O/r04a_bench_default.json.log; tail -c 2500 $O/r04a_bench_default.json.log

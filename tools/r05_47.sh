@@ -1,7 +1,7 @@
 #!/bin/bash
 export TMPDIR=/tmp O=gpurun_out
 t0=$(date +%s)
-python bench.py > $O/r05bc_bench_default.json.log 2> $O/r05bc_bench_default.err
+python bench.py --full > $O/r05bc_bench_default.json.log 2> $O/r05bc_bench_default.err
 echo "rc=$? wall=$(( $(date +%s) - t0 )) s"
 tail -2 $O/r05bc_bench_default.err
 python - <<PY

@@ -8,7 +8,7 @@ timeout 900 python tools/layer_error_budget.py $O/r05a_layer_error_budget.json >
 python tools/dump_trunk_operands.py $O/trunk_acts.bin $O/trunk_weights.bin
 CEIL_SECONDS=4 CEIL_SKIP_DUTY=1 timeout 900 tools/mfma_ceiling $O/trunk_acts.bin $O/trunk_weights.bin > $O/r05a_mfma_ceiling_orders.txt 2>&1
 rm -f $O/trunk_acts.bin $O/trunk_weights.bin
-timeout 900 python bench.py --details $O/r05a_bench_details.json > $O/r05a_bench_feature_b32.json.log 2> $O/r05a_bench.err
+timeout 900 python bench.py --full --details $O/r05a_bench_details.json > $O/r05a_bench_feature_b32.json.log 2> $O/r05a_bench.err
 tail -5 $O/r05a_bench.err
 cat $O/r05a_tests_new.txt
 tail -3 $O/r05a_layer_error_budget.txt

@@ -3,4 +3,4 @@
 O=gpurun_out; mkdir -p $O
 timeout 900 python -m pytest tests -m gpu -x -q 2>&1 | tail -8 > $O/r06a_gpu_tests.txt; cat $O/r06a_gpu_tests.txt
 bash tools/ab_variants.sh rolled 2>&1 | tee $O/r06a_ab_c34_bodies.txt
-timeout 1200 python bench.py > $O/r06a_bench_default.json.log 2> $O/r06a_bench_default.err; tail -c 3000 $O/r06a_bench_default.json.log
+timeout 1200 python bench.py --full > $O/r06a_bench_default.json.log 2> $O/r06a_bench_default.err; tail -c 3000 $O/r06a_bench_default.json.log
