@@ -175,6 +175,11 @@ typedef struct srbh_rrdbnet_desc {
     srbh_conv_w conv_body, conv_up1, conv_up2, conv_hr;
     srbh_conv_w conv_last;      /* cout padded to 32; only used when want_forward */
     int num_out_ch;
+    const srbh_conv_w* rdb_b16; /* NULL, or the same [num_block*3*5] convs as bf16 packs (srbh_pack_conv3x3_b16; bias pointers as in `rdb`):
+                                 * srbh_rrdbnet_forward then runs the dense blocks on bf16 operands -- bf16 planes, v_mfma_f32_32x32x16_bf16,
+                                 * fp32 RRDB streams as before, the trunk's output planes rounded to fp16 for conv_body, which with the
+                                 * up-sampler tail keeps its fp16 operands.  Environment SRBH_TRUNK_BF16=0 restores the fp16 trunk (A/B).
+                                 * The training entry points below always use `rdb`. */
 } srbh_rrdbnet_desc;
 
 size_t srbh_rrdbnet_workspace_bytes(int B, int H, int W, int want_forward);
@@ -233,7 +238,8 @@ int srbh_trunk_wgrad(int num_block, const void* dense_all, size_t dense_stride, 
 
 /* Synchronises `stream` and returns 0 if the last srbh_rrdbnet_forward on this workspace completed normally, or a
  * negative code if the persistent trunk kernel gave up waiting for a neighbour workgroup (its spins are bounded so a
- * scheduling problem shows up as an error here instead of a hung GPU).  Set SRBH_PERSISTENT=0 to force per-layer launches. */
+ * scheduling problem shows up as an error here instead of a hung GPU).  Set SRBH_PERSISTENT=0 to force per-layer launches (the same bits),
+ * SRBH_TRUNK_BF16=0 to run the dense blocks on fp16 instead of bf16 operands (see srbh_rrdbnet_desc.rdb_b16). */
 int srbh_rrdbnet_last_status(const void* ws, int B, int H, int W, int want_forward, void* stream);
 
 /* Workgroups per launch of the persistent tail convs (conv_up1 / conv_up2 / conv_hr, SR/rrdbnet_arch.py:234-239) issued by the calling host

@@ -166,6 +166,7 @@ class RRDBNetDesc(C.Structure):
         ("rdb", C.POINTER(ConvW)),
         ("conv_body", ConvW), ("conv_up1", ConvW), ("conv_up2", ConvW), ("conv_hr", ConvW),
         ("conv_last", ConvW), ("num_out_ch", C.c_int),
+        ("rdb_b16", C.POINTER(ConvW)),
     ]
 
 

@@ -202,7 +202,8 @@ __global__ __launch_bounds__(256) void act16_channel_sum_kernel(const char* __re
 // Thread = (4 consecutive pixels of a row, 4 consecutive output channels); 16 lanes cover the 64 channels of a pixel
 // group so every store instruction writes whole 256-byte pixel records.  Weights sit in LDS as [ic*9+tap][64] and are
 // read as float4 broadcasts; each input value is loaded once and reused for the 4 channels x up to 3 pixels it touches.
-template <int CIN>
+// BF16 = 1: the 16-bit planes in bf16 (RNE), the first planes of the bf16 inference trunk
+template <int CIN, int BF16 = 0>
 __global__ __launch_bounds__(256) void conv_first_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                          const float* __restrict__ bias, int B, int cin_rt, int H, int W,
                                                          float* ra, float* rb, float* rc, char* out16, int row_b,
@@ -267,7 +268,10 @@ __global__ __launch_bounds__(256) void conv_first_kernel(const float* __restrict
             _Float16* o = (_Float16*)(out16 + b * img_b + (long)(og >> 3) * plane_b + (long)(yy + 1) * row_b +
                                       (xx + 1) * PIX_B + (og & 7) * 8);
             typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-            *(half4*)o = half4{(_Float16)acc[p][0], (_Float16)acc[p][1], (_Float16)acc[p][2], (_Float16)acc[p][3]};
+            if constexpr (BF16)
+                *(uint2*)o = uint2{bf16x2_rne(acc[p][0], acc[p][1]), bf16x2_rne(acc[p][2], acc[p][3])};
+            else
+                *(half4*)o = half4{(_Float16)acc[p][0], (_Float16)acc[p][1], (_Float16)acc[p][2], (_Float16)acc[p][3]};
         }
     }
 }
@@ -505,16 +509,29 @@ extern "C" int srbh_act16_channel_sum(const void* src, int B, int H, int W, int 
 extern "C" int srbh_conv_first_f32(const float* x, const float* w, const float* bias, int B, int cin, int H, int W,
                                    float* ra, float* rb, float* rc, void* out16, int out16_chunks_total,
                                    void* stream) {
+    return srbh::conv_first_f32(x, w, bias, B, cin, H, W, ra, rb, rc, out16, out16_chunks_total, 0, stream);
+}
+
+int srbh::conv_first_f32(const float* x, const float* w, const float* bias, int B, int cin, int H, int W, float* ra, float* rb, float* rc,
+                         void* out16, int out16_chunks_total, int bf16, void* stream) {
     SRBH_REQUIRE(x && w && B > 0 && cin > 0 && H > 0 && W > 0, "srbh_conv_first_f32: bad arguments");
     SRBH_REQUIRE(!out16 || out16_chunks_total >= 2, "srbh_conv_first_f32: out16 needs >= 2 chunk planes");
     Act16Geo g = act16_geo(B, out16_chunks_total > 0 ? out16_chunks_total : 2, H, W);
     SRBH_REQUIRE(cin <= 56, "srbh_conv_first_f32: at most 56 input channels (got %d)", cin);
     long total = (long)B * H * ((W + 3) / 4) * 16;
     const size_t lds = (size_t)cin * 9 * 64 * sizeof(float);
-    if (cin == 3)
+    if (cin == 3 && bf16)
+        hipLaunchKernelGGL((conv_first_kernel<3, 1>), dim3((total + 255) / 256), dim3(256), lds, (hipStream_t)stream, x, w, bias,
+                           B, cin, H, W, ra, rb, rc, (char*)out16, g.row_b, g.plane_b, g.img_b);
+    else if (cin == 3)
         hipLaunchKernelGGL(conv_first_kernel<3>, dim3((total + 255) / 256), dim3(256), lds, (hipStream_t)stream, x, w, bias,
                            B, cin, H, W, ra, rb, rc, (char*)out16, g.row_b, g.plane_b, g.img_b);
-    else {
+    else if (bf16) {
+        if (lds > 65536)
+            SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)conv_first_kernel<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 56 * 9 * 64 * 4)));
+        hipLaunchKernelGGL((conv_first_kernel<0, 1>), dim3((total + 255) / 256), dim3(256), lds, (hipStream_t)stream, x, w, bias,
+                           B, cin, H, W, ra, rb, rc, (char*)out16, g.row_b, g.plane_b, g.img_b);
+    } else {
         if (lds > 65536)
             SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)conv_first_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 56 * 9 * 64 * 4)));
         hipLaunchKernelGGL(conv_first_kernel<0>, dim3((total + 255) / 256), dim3(256), lds, (hipStream_t)stream, x, w, bias,

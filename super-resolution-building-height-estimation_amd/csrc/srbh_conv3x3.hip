@@ -113,6 +113,7 @@ static int conv3x3_impl(const srbh_conv3x3_args* a, const int bf16, const void* 
         p.mask16 = (const char*)mask16 + (long)mask_chunk0 * gm.plane_b;
         p.mask_img_b = gm.img_b; p.mask_plane_b = gm.plane_b; p.mask_row_b = gm.row_b;
     }
+    if (bf16 == 2) return a->cout == 64 ? launch<2, 0, 2>(p, stream) : launch<1, 0, 2>(p, stream);
     if (bf16) return a->cout == 64 ? launch<2, 0, 1>(p, stream) : launch<1, 0, 1>(p, stream);
 
     if (a->upsample2x) return a->cout == 64 ? launch<2, 1>(p, stream) : launch<1, 1>(p, stream);
@@ -127,5 +128,9 @@ extern "C" int srbh_conv3x3_f16(const srbh_conv3x3_args* a, void* stream) { retu
  * activation plane(s) mask16[chunk mask_chunk0 ..] (post-activation > 0 ? 1 : 0.2), before the 16-bit / fp32 stores. */
 extern "C" int srbh_conv3x3_x16(const srbh_conv3x3_args* a, int bf16, const void* mask16, int mask_chunks_total, int mask_chunk0,
                                 void* stream) {
-    return conv3x3_impl(a, bf16, mask16, mask_chunks_total, mask_chunk0, stream);
+    return conv3x3_impl(a, bf16 ? 1 : 0, mask16, mask_chunks_total, mask_chunk0, stream);
+}
+
+int srbh::conv3x3_trunk_b16(const srbh_conv3x3_args* a, const int out_f16, void* stream) {
+    return conv3x3_impl(a, out_f16 ? 2 : 1, nullptr, 0, 0, stream);
 }

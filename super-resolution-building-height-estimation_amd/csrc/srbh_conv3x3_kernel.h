@@ -87,6 +87,7 @@ __device__ __forceinline__ int xcd_remap(int bid, int n) {
 // write-through (sc1) stores so that a neighbouring workgroup can consume them inside the same launch.
 // BF = 1: bf16 operands (gradients: fp32's exponent range, no loss scaling) -- the staged 16-bit records and the packed weights are
 // bf16, the products run on v_mfma_f32_32x32x16_bf16 and a 16-bit output is rounded to bf16 (RNE); everything else is identical.
+// BF = 2: bf16 operands as BF = 1, the 16-bit output rounded to fp16 (the bf16 inference trunk's last conv5: its planes leave for conv_body).
 template <int CB, int UPS, int ABL, int PERSIST, int BF = 0>
 __device__ __forceinline__ void conv_tile(const KParams& p, char* smem, const int img, const int Y0, const int X0,
                                           unsigned long long* tstamp) {
@@ -363,7 +364,7 @@ __device__ __forceinline__ void conv_tile(const KParams& p, char* smem, const in
                     }
                     if (p.out16) {
                         half8 hv;
-                        if constexpr (BF) {
+                        if constexpr (BF == 1) {
                             typedef unsigned uint4e __attribute__((ext_vector_type(4)));
                             const uint4e u0 = __builtin_bit_cast(uint4e, v0), u1 = __builtin_bit_cast(uint4e, v1);
                             unsigned r[8];

@@ -81,7 +81,14 @@ size_t ptrunk_aux_bytes(int B, int tiles_per_img);
 size_t ptrunk_err_offset(int B, int tiles_per_img);
 int ptail_run(const srbh_conv3x3_args* a, hipStream_t stream, int* used);
 int ptrunk_run(const srbh_rrdbnet_desc* d, void* dense0, void* dense1, float* xr, float* xrr, int B, int H, int W,
-               void* aux, hipStream_t stream, int* used, int* final_cur, long train_stride = 0, const void* mask = nullptr, long mask_stride = 0);
+               void* aux, hipStream_t stream, int* used, int* final_cur, long train_stride = 0, const void* mask = nullptr, long mask_stride = 0,
+               bool bf16 = false);
+// the inference trunk's bf16 form, per layer (srbh_rrdbnet_forward with SRBH_PERSISTENT=0): srbh_conv3x3_x16(bf16 = 1) for conv1..conv4 and the
+// inner conv5s; out_f16 = 1: bf16 operands, the 16-bit output rounded to fp16 (the last conv5: the trunk's output planes, conv_body reads fp16)
+int conv3x3_trunk_b16(const srbh_conv3x3_args* a, int out_f16, void* stream);
+// srbh_conv_first_f32 with the 16-bit planes in bf16 (bf16 != 0): the first planes of the bf16 inference trunk
+int conv_first_f32(const float* x, const float* w, const float* bias, int B, int cin, int H, int W, float* ra, float* rb, float* rc,
+                   void* out16, int out16_chunks_total, int bf16, void* stream);
 
 
 #if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)

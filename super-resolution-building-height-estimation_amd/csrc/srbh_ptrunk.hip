@@ -143,10 +143,13 @@ static int device_table(const std::vector<PLayer>& tab, PLayer** out) {
 // bytes apart (dense1 ignored), every plane is stored whole, and the trunk's fp32 output goes to `xr` in pixel order.
 // mask != nullptr = the BACKWARD of the dense blocks (srbh_rrdbnet_trunk_train_backward_persistent; needs train_stride > 0): `d` holds the gradient convs'
 // bf16 packs in running (reverse) order, mask / mask_stride walk the saved forward buffers.
+// bf16 = the INFERENCE forward on bf16 operands (ptrunk3_kernel<0, 0, 1>; inference only: train_stride == 0, no mask): `d` holds bf16 packs
+// (srbh_pack_conv3x3_b16), dense0's planes 0..1 hold bf16, the trunk's output planes come out fp16.
 int ptrunk_run(const srbh_rrdbnet_desc* d, void* dense0, void* dense1, float* xr, float* xrr, int B, int H, int W,
-               void* aux, hipStream_t stream, int* used, int* final_cur, long train_stride, const void* mask, long mask_stride) {
+               void* aux, hipStream_t stream, int* used, int* final_cur, long train_stride, const void* mask, long mask_stride, bool bf16) {
     *used = 0;
     if (mask && train_stride <= 0) return SRBH_OK;
+    SRBH_REQUIRE(!bf16 || (train_stride == 0 && !mask), "ptrunk_run: the bf16 form is the inference forward only");
     if (W != TILE_W || (H % TILE_H) != 0 || d->num_block <= 0 || d->num_block > MAX_BLOCKS) return SRBH_OK;
     int dev = 0;
     SRBH_HIP(hipGetDevice(&dev));
@@ -159,6 +162,7 @@ int ptrunk_run(const srbh_rrdbnet_desc* d, void* dense0, void* dense1, float* xr
         SRBH_HIP(hipFuncSetAttribute((const void*)ptrunk3_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B));
         SRBH_HIP(hipFuncSetAttribute((const void*)ptrunk3_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B));
         SRBH_HIP(hipFuncSetAttribute((const void*)ptrunk3_kernel<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B));
+        SRBH_HIP(hipFuncSetAttribute((const void*)ptrunk3_kernel<0, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B));
     });
     int per_cu = 0;
     SRBH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ptrunk3_kernel<0>, 256, LDS_B));
@@ -222,13 +226,15 @@ int ptrunk_run(const srbh_rrdbnet_desc* d, void* dense0, void* dense1, float* xr
             const char* e = getenv("SRBH_PT_WT");
             pp.force_wt = (e && atoi(e) == 1) ? 1 : 0;
         }
-        if (getenv("SRBH_PT_PROF") && !g_ptrunk_prof)
+        if (getenv("SRBH_PT_PROF") && !bf16 && !g_ptrunk_prof)      // (the developer timeline exists for the fp16 form only)
             SRBH_HIP(hipMalloc(&g_ptrunk_prof, (size_t)ncu * MAX_BLOCKS * 15 * 6 * 8));
-        pp.prof = g_ptrunk_prof;
+        pp.prof = bf16 ? nullptr : g_ptrunk_prof;
         if (g_trunk_timing && b0 == 0) SRBH_HIP(hipEventRecord(g_trunk_ev[0], stream));
         g_trunk_kernel = "ptrunk3_kernel";
         if (mask)
             hipLaunchKernelGGL((ptrunk3_kernel<0, 1>), dim3(pp.nblocks), dim3(256), LDS_B, stream, pp);
+        else if (bf16)
+            hipLaunchKernelGGL((ptrunk3_kernel<0, 0, 1>), dim3(pp.nblocks), dim3(256), LDS_B, stream, pp);
         else if (pp.prof)
             hipLaunchKernelGGL((ptrunk3_kernel<1>), dim3(pp.nblocks), dim3(256), LDS_B, stream, pp);
         else
@@ -236,7 +242,7 @@ int ptrunk_run(const srbh_rrdbnet_desc* d, void* dense0, void* dense1, float* xr
         SRBH_HIP(hipGetLastError());
     }
     if (g_trunk_timing) { SRBH_HIP(hipEventRecord(g_trunk_ev[1], stream)); g_trunk_ev_recorded = 1; }
-    if (getenv("SRBH_PT_PROF") && g_ptrunk_prof) {   // developer aid: cycles vs wall clock of the real forward
+    if (getenv("SRBH_PT_PROF") && g_ptrunk_prof && !bf16) {   // developer aid: cycles vs wall clock of the real forward
         SRBH_HIP(hipStreamSynchronize(stream));
         const int nblk = (B < imgs_per_launch ? B : imgs_per_launch) * tpi;
         std::vector<unsigned long long> h((size_t)nblk * nl * 6);

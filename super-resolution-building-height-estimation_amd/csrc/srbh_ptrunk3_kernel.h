@@ -92,7 +92,14 @@
 // pp.mask_stride, plane 5 - kk) instead of applying bias + LeakyReLU, and every plane is kept (the weight gradients read them).  The residual
 // recurrences are the forward's own: with the stream held as 0.04 x the gradient, `x = 0.2 conv5 + x` is g5' = 0.2 (dx + cur) and the
 // RRDB-closing `x = 0.2 x + x_rrdb` is the RRDB's skip connection (see srbh_rrdbnet_trunk_train_backward_persistent).
-template <int PROF, int BW = 0>
+// BF = 1 (round 8): the INFERENCE forward on bf16 operands -- bf16 dense planes and weight packs (srbh_pack_conv3x3_b16),
+// v_mfma_f32_32x32x16_bf16, the epilogues rounding RNE to bf16 where the fp16 form rounds to fp16 -- on the same protocol, tiling, LDS map
+// and instruction schedule.  The matrix core's clock under the package power cap is set by how many operand bits toggle
+// (profiles/r06d_mfma_ceiling.txt); bf16's 8-bit significand switches less per MFMA than fp16's 11 bits: on the real trunk operands the
+// capped clock rises by ~8 % (profiles/r08a_mfma_ceiling_bf16.txt).  The fp32 RRDB stream stays fp32, and the LAST RDB rounds the trunk's
+// output planes to fp16 as the fp16 form does (`f16out`): conv_body and the up-sampler tail read fp16.  Training forward and backward
+// never run this form.
+template <int PROF, int BW = 0, int BF = 0>
 __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -440,7 +447,7 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
-                if constexpr (BW)
+                if constexpr (BW || BF)
                     acc[mb][i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, A[g & 1][dy][mb]), __builtin_bit_cast(bf16x8, P[g & 1][i + dy]), acc[mb][i], 0, 0, 0);
                 else
                     acc[mb][i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[g & 1][dy][mb], P[g & 1][i + dy], acc[mb][i], 0, 0, 0);
@@ -565,12 +572,17 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
                 const floatx4 ws = w * 0.2f;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) asm("v_max_f32 %0, %1, %2" : "=v"(w[q]) : "v"(w[q]), "v"(ws[q]));
+                if constexpr (BF) {       // bf16, RNE (as the per-layer kernel's bf16 form)
+                    hp[g][0] = bf16x2_rne(w[0], w[1]);
+                    hp[g][1] = bf16x2_rne(w[2], w[3]);
+                } else {
                 half4 h4;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) h4[q] = (_Float16)w[q];
                 const uint2 u = __builtin_bit_cast(uint2, h4);
                 hp[g][0] = u.x;
                 hp[g][1] = u.y;
+                }
             }
             }
 #pragma unroll
@@ -591,7 +603,8 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
     };
     // one row of x (channel block mb) -> 16-bit fragments, kept (mb == 1), written into the next RDB's resident plane (mb == 0, to_lds) and
     // stored where somebody reads them from memory
-    auto x_row_out = [&](const int mb, const int i, char* obase, const bool st, const bool to_lds = false) {
+    // (BF: bf16, except behind the last RDB -- f16out -- whose planes are the trunk's output: fp16 for conv_body)
+    auto x_row_out = [&](const int mb, const int i, char* obase, const bool st, const bool to_lds, const bool f16out) {
         const int Y = Y0 + wr * 4 + i;
         unsigned hp[4][2];
 #pragma unroll
@@ -606,6 +619,9 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
                 }
                 hp[g][0] = r[0] | (r[1] << 16);
                 hp[g][1] = r[2] | (r[3] << 16);
+            } else if (BF && !f16out) {
+                hp[g][0] = bf16x2_rne(xres[mb][i][g][0], xres[mb][i][g][1]);
+                hp[g][1] = bf16x2_rne(xres[mb][i][g][2], xres[mb][i][g][3]);
             } else {
                 half4 h4;
 #pragma unroll
@@ -635,7 +651,8 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
     // (x = 0.2 x + x_rrdb, the RRDB-level stream lives in memory): that is a SECOND pass over the registers behind a uniform
     // branch -- as a flag inside one body hipcc if-converted it into 128 selects, as two bodies the 160 live registers met in
     // phis and spilled.  In an RRDB-closing RDB the first pass stores nothing (its fp16 values are not final).
-    auto epi64 = [&](floatx16 (&acc)[2][4], char* obase, const bool r2, const bool r2_pixel, const bool x1_halo_only, const bool keep, const bool out_px) {
+    auto epi64 = [&](floatx16 (&acc)[2][4], char* obase, const bool r2, const bool r2_pixel, const bool x1_halo_only, const bool keep, const bool out_px,
+                     const bool f16out) {
         floatx4 bias4[2][4];
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb)
@@ -679,7 +696,7 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
                     tt += bias4[mb][g];
                     xres[mb][i][g] = tt * 0.2f + xres[mb][i][g];
                 }
-                if (!r2) x_row_out(mb, i, obase, keep || (!P3_SEAM && mb == 0) || !x1_halo_only || halo, x1_halo_only);   // (RRDB-closing: the fp16 values are not final yet)
+                if (!r2) x_row_out(mb, i, obase, keep || (!P3_SEAM && mb == 0) || !x1_halo_only || halo, x1_halo_only, f16out);   // (RRDB-closing: the fp16 values are not final yet)
             }
         }
         if (r2) {
@@ -690,7 +707,7 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
                 for (int mb = 0; mb < 2; ++mb) {
 #pragma unroll
                     for (int g = 0; g < 4; ++g) xres[mb][i][g] = xres[mb][i][g] * 0.2f + a2[slot][mb][g];
-                    x_row_out(mb, i, obase, keep || (!P3_SEAM && mb == 0) || !x1_halo_only || halo, x1_halo_only);
+                    x_row_out(mb, i, obase, keep || (!P3_SEAM && mb == 0) || !x1_halo_only || halo, x1_halo_only, f16out);
                 }
                 // the RRDB-level stream goes back to memory (fragment order): private to this workgroup
                 // (out_px: behind the LAST RDB of a training forward it is the trunk's output: to `xr`, pixel order = NHWC)
@@ -870,7 +887,7 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
             const bool r2 = (rdb % 3) == 2;
             if (PROF) p2 = __builtin_amdgcn_s_memtime();
             epi64(acc, dnxt - (long)Y0 * pp.row_b, r2, rdb == 2, P3_SKIPST && P3_S1 && rdb + 1 < nrdb, P3_TRAIN && pp.keep_all != 0,
-                  P3_TRAIN && pp.out_pixel != 0 && rdb + 1 == nrdb);   // (the last x goes out whole: conv_body reads it)
+                  P3_TRAIN && pp.out_pixel != 0 && rdb + 1 == nrdb, BF && rdb + 1 == nrdb);   // (the last x goes out whole: conv_body reads it)
             if (PROF) p3 = __builtin_amdgcn_s_memtime();
             // RDB seam: the next conv1's first chunk is THIS layer's output on the neighbours: publish now, then wait for them
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -76,8 +76,16 @@ extern "C" int srbh_rrdbnet_forward(const srbh_rrdbnet_desc* d, const float* x, 
     void* U3 = base + L.u3;
     void* U4 = base + L.u4;
 
-    int rc = srbh_conv_first_f32(x, d->conv_first_w, d->conv_first_b, B, d->num_in_ch, H, W, feat, xr, xrr, D[0], 6,
-                                 stream);
+    // The dense blocks run on bf16 operands when the descriptor carries bf16 packs of the trunk convs (d->rdb_b16) and SRBH_TRUNK_BF16 is not
+    // "0" (read on every call: an A/B switch).  conv_first writes the trunk's first planes as bf16, every dense-block conv rounds its 16-bit output
+    // to bf16, and the last conv5 rounds the trunk's output planes to fp16 (the fp32 RRDB streams are fp32 either way): conv_body onwards runs
+    // on exactly the fp16 path.  Persistent and per-layer forms compute the same bits in both precisions.
+    bool bf16 = false;
+    if (d->rdb_b16 && d->num_block > 0) {
+        const char* env = getenv("SRBH_TRUNK_BF16");
+        bf16 = !(env && env[0] == '0');
+    }
+    int rc = conv_first_f32(x, d->conv_first_w, d->conv_first_b, B, d->num_in_ch, H, W, feat, xr, xrr, D[0], 6, bf16 ? 1 : 0, stream);
     if (rc) return rc;
 
     srbh_conv3x3_args a;
@@ -87,20 +95,22 @@ extern "C" int srbh_rrdbnet_forward(const srbh_rrdbnet_desc* d, const float* x, 
         const char* env = getenv("SRBH_PERSISTENT");
         const bool want = !(env && env[0] == '0');
         if (want) {
-            rc = ptrunk_run(d, D[0], D[1], xr, xrr, B, H, W, base + L.aux, (hipStream_t)stream, &used_persistent, &cur);
+            srbh_rrdbnet_desc dt = *d;
+            if (bf16) dt.rdb = d->rdb_b16;
+            rc = ptrunk_run(&dt, D[0], D[1], xr, xrr, B, H, W, base + L.aux, (hipStream_t)stream, &used_persistent, &cur, 0, nullptr, 0, bf16);
             if (rc) return rc;
         }
     }
     for (int blk = 0; !used_persistent && blk < d->num_block; ++blk) {
         for (int r = 0; r < 3; ++r) {
-            const srbh_conv_w* cw = d->rdb + (blk * 3 + r) * 5;
+            const srbh_conv_w* cw = (bf16 ? d->rdb_b16 : d->rdb) + (blk * 3 + r) * 5;
             for (int k = 0; k < 4; ++k) {  // conv1..conv4: lrelu(conv(cat(x, x1..xk)))
                 a = srbh_conv3x3_args{};
                 a.in = D[cur]; a.in_chunks_total = 6; a.in_chunk0 = 0; a.in_chunks = 2 + k;
                 a.w = cw[k].w; a.bias = cw[k].bias; a.cout = 32;
                 a.B = B; a.H = H; a.W = W; a.lrelu = 1;
                 a.out16 = D[cur]; a.out16_chunks_total = 6; a.out16_chunk0 = 2 + k;
-                if ((rc = srbh_conv3x3_f16(&a, stream))) return rc;
+                if ((rc = bf16 ? conv3x3_trunk_b16(&a, 0, stream) : srbh_conv3x3_f16(&a, stream))) return rc;
             }
             a = srbh_conv3x3_args{};  // conv5 + x5*0.2 + x (+ out*0.2 + x_rrdb at the end of the RRDB)
             a.in = D[cur]; a.in_chunks_total = 6; a.in_chunk0 = 0; a.in_chunks = 6;
@@ -109,7 +119,8 @@ extern "C" int srbh_rrdbnet_forward(const srbh_rrdbnet_desc* d, const float* x, 
             a.res_scale = 0.2f; a.res1 = xr; a.res1_update = 1;
             if (r == 2) { a.res2 = xrr; a.res2_scale = 0.2f; a.res2_update = 1; }
             a.out16 = D[cur ^ 1]; a.out16_chunks_total = 6; a.out16_chunk0 = 0;
-            if ((rc = srbh_conv3x3_f16(&a, stream))) return rc;
+            const bool last = blk + 1 == d->num_block && r == 2;     // (bf16: the trunk's output planes go out as fp16)
+            if ((rc = bf16 ? conv3x3_trunk_b16(&a, last ? 1 : 0, stream) : srbh_conv3x3_f16(&a, stream))) return rc;
             cur ^= 1;
         }
     }

@@ -177,7 +177,9 @@ class RRDBNet(nn.Module):
         params = [t for c in convs for t in (c.weight, c.bias) if t is not None] + [self.conv_first.weight, self.conv_first.bias]
         if all(t.device == dev and t.dtype == torch.float32 and t.is_contiguous() for t in params):
             return self._pack_in_place(dev, convs, params)
-        sizes = [L.srbh_wpack16_bytes(c.out_channels, c.in_channels) for c in convs]
+        n_rdb = num_block * 15
+        # the dense-block convs twice: fp16 packs (training paths, SRBH_TRUNK_BF16=0) and bf16 packs (the inference trunk), behind all convs
+        sizes = [L.srbh_wpack16_bytes(c.out_channels, c.in_channels) for c in convs + convs[:n_rdb]]
         offs, tot = [], 0
         for s in sizes:
             offs.append(tot)
@@ -197,11 +199,16 @@ class RRDBNet(nn.Module):
                 bbuf[bo:bo + c.out_channels] = c.bias.detach().float()
             boffs.append(bo)
             bo += bp
-        n_rdb = num_block * 15
+        for i, (c, w) in enumerate(zip(convs[:n_rdb], keep)):
+            _lib.check(L.srbh_pack_conv3x3_b16(w.data_ptr(), c.out_channels, c.in_channels, wbuf.data_ptr() + offs[len(convs) + i], st),
+                       "pack_conv3x3_b16")
         rdb_arr = (_lib.ConvW * max(n_rdb, 1))()
+        rdb_b16 = (_lib.ConvW * max(n_rdb, 1))()
         for i in range(n_rdb):
             rdb_arr[i].w = wbuf.data_ptr() + offs[i]
             rdb_arr[i].bias = bbuf.data_ptr() + 4 * boffs[i]
+            rdb_b16[i].w = wbuf.data_ptr() + offs[len(convs) + i]
+            rdb_b16[i].bias = rdb_arr[i].bias
         d = _lib.RRDBNetDesc()
         d.num_in_ch = num_in_ch
         d.num_block = num_block
@@ -214,8 +221,9 @@ class RRDBNet(nn.Module):
             cw = _lib.ConvW(wbuf.data_ptr() + offs[n_rdb + j], bbuf.data_ptr() + 4 * boffs[n_rdb + j])
             setattr(d, name, cw)
         d.num_out_ch = num_out_ch
+        d.rdb_b16 = C.cast(rdb_b16, C.POINTER(_lib.ConvW)) if n_rdb else None
         torch.cuda.current_stream().synchronize()  # `keep` temporaries may be freed after this
-        return (wbuf, bbuf, cf_w, cf_b, rdb_arr), d
+        return (wbuf, bbuf, cf_w, cf_b, rdb_arr, rdb_b16), d
 
     def _pack_in_place(self, dev, convs, params):
         """The usual case -- fp32 parameters living on `dev`: ONE launch (srbh_pack_conv3x3_many) rewrites every pack and the padded bias table IN
@@ -228,7 +236,10 @@ class RRDBNet(nn.Module):
         plan = self.__dict__.get("_pack_plan")
         if plan is None or plan["key"] != key:
             num_in_ch, num_out_ch, num_feat, num_block, num_grow_ch = self._geom
-            sizes = [L.srbh_wpack16_bytes(c.out_channels, c.in_channels) for c in convs]
+            n_rdb = num_block * 15
+            # the dense-block convs twice: fp16 packs (training paths, SRBH_TRUNK_BF16=0) and bf16 packs (the inference trunk), behind all
+            # convs; both are rewritten by the same launch, so a weight update reaches either form
+            sizes = [L.srbh_wpack16_bytes(c.out_channels, c.in_channels) for c in convs + convs[:n_rdb]]
             offs, tot = [], 0
             for sz in sizes:
                 offs.append(tot)
@@ -242,16 +253,20 @@ class RRDBNet(nn.Module):
                 bo += bp
             desc_t = np.dtype([("w", np.uint64), ("packed", np.uint64), ("bias_src", np.uint64), ("bias_dst", np.uint64), ("cout", np.int32), ("cin", np.int32),
                                ("bf16", np.int32), ("pad", np.int32)])
-            tab = np.zeros(len(convs), dtype=desc_t)
+            tab = np.zeros(len(convs) + n_rdb, dtype=desc_t)
             for i, c in enumerate(convs):
                 tab[i] = (c.weight.data_ptr(), wbuf.data_ptr() + offs[i], 0 if c.bias is None else c.bias.data_ptr(),
                           0 if c.bias is None else bbuf.data_ptr() + 4 * boffs[i], c.out_channels, c.in_channels, 0, 0)
+            for i, c in enumerate(convs[:n_rdb]):      # (bias table: written by the fp16 entry)
+                tab[len(convs) + i] = (c.weight.data_ptr(), wbuf.data_ptr() + offs[len(convs) + i], 0, 0, c.out_channels, c.in_channels, 1, 0)
             table = torch.from_numpy(tab.view(np.uint8).copy()).to(dev)
-            n_rdb = num_block * 15
             rdb_arr = (_lib.ConvW * max(n_rdb, 1))()
+            rdb_b16 = (_lib.ConvW * max(n_rdb, 1))()
             for i in range(n_rdb):
                 rdb_arr[i].w = wbuf.data_ptr() + offs[i]
                 rdb_arr[i].bias = bbuf.data_ptr() + 4 * boffs[i]
+                rdb_b16[i].w = wbuf.data_ptr() + offs[len(convs) + i]
+                rdb_b16[i].bias = rdb_arr[i].bias
             d = _lib.RRDBNetDesc()
             d.num_in_ch = num_in_ch
             d.num_block = num_block
@@ -261,8 +276,9 @@ class RRDBNet(nn.Module):
             for j, name in enumerate(("conv_body", "conv_up1", "conv_up2", "conv_hr", "conv_last")):
                 setattr(d, name, _lib.ConvW(wbuf.data_ptr() + offs[n_rdb + j], bbuf.data_ptr() + 4 * boffs[n_rdb + j]))
             d.num_out_ch = num_out_ch
-            plan = self.__dict__["_pack_plan"] = {"key": key, "bufs": (wbuf, bbuf, table, rdb_arr, params), "desc": d, "table": table, "n": len(convs),
-                                                  "max_elems": max(sizes) // 2}
+            d.rdb_b16 = C.cast(rdb_b16, C.POINTER(_lib.ConvW)) if n_rdb else None
+            plan = self.__dict__["_pack_plan"] = {"key": key, "bufs": (wbuf, bbuf, table, rdb_arr, rdb_b16, params), "desc": d, "table": table,
+                                                  "n": len(tab), "max_elems": max(sizes) // 2}
         _lib.check(L.srbh_pack_conv3x3_many(plan["table"].data_ptr(), plan["n"], plan["max_elems"], _lib.stream_ptr()), "pack_conv3x3_many")
         return plan["bufs"], plan["desc"]
 

@@ -12,6 +12,8 @@
 //                    tile per CU has to move through L2 -> LDS, so this is the ceiling of the tiling, not of the kernel
 //   mode duty<p>   : MFMA bursts with idle gaps (s_sleep) so that the matrix core is busy ~p % of the cycles: what the chip gives
 //                    back in clock when the kernel idles (the trunk: 59 % busy)
+//   CEIL_BF16=1    : after each operand set's fp16 rows, the three rows above again on v_mfma_f32_32x32x16_bf16 with the same data
+//                    rounded RNE to bf16: does the narrower significand lower the switching energy, and so lift the capped clock?
 // operand data: zeros | random fp16 in [-0.5, 0.5) | a dump of real trunk activations / weights (tools/dump_trunk_operands.py)
 //   hipcc --offload-arch=gfx950 -O3 tools/mfma_ceiling.hip -o tools/mfma_ceiling ; tools/mfma_ceiling [acts.bin weights.bin]
 #include <hip/hip_runtime.h>
@@ -21,11 +23,20 @@
 #include <cstring>
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float floatx16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+// BF = 1: the same instruction stream on v_mfma_f32_32x32x16_bf16; the operand buffers then hold bf16 bit patterns (host-rounded RNE
+// from the fp16 data), carried through the kernel in the half8 registers and bit-cast at the MFMA
+template <int BF>
+__device__ __forceinline__ floatx16 mfma32(const half8 a, const half8 b, const floatx16 c) {
+    if constexpr (BF) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+}
 
 struct Out { unsigned long long cyc, real; };
 
 // MODE 0: MFMA only; 1: MFMA + LDS reads (9 per 12 MFMAs); 2: duty-cycled MFMA (sleep after each burst of 32); 3: as 1 + the weight LDS-DMA stream
-template <int MODE>
+template <int MODE, int BF = 0>
 __global__ __launch_bounds__(256, 1) void ceiling_kernel(const half8* __restrict__ wsrc, const half8* __restrict__ asrc, int nfrag, int iters, int sleep_n,
                                                          Out* out, float* sink, const char* wstream = nullptr, long wstream_b = 0) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -64,7 +75,7 @@ __global__ __launch_bounds__(256, 1) void ceiling_kernel(const half8* __restrict
             for (int u = 0; u < NG; ++u) {
 #pragma unroll
                 for (int m = 0; m < 12; ++m) {
-                    c[m & 3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(v[u & 1][6 + m / 4], v[u & 1][(m & 3) + m / 4], c[m & 3], 0, 0, 0);
+                    c[m & 3] = mfma32<BF>(v[u & 1][6 + m / 4], v[u & 1][(m & 3) + m / 4], c[m & 3]);
                     if (m < 9) v[(u + 1) & 1][m] = *(const half8*)(base + ((u & 3) * 9 + m) * 1024);      // (immediate offsets, as in the trunk)
                     if (MODE == 3 && m == 10 && u < 5) {
                         // 18 KiB per workgroup and step = 4.5 KiB per wave: 4 full statements + 1 that only waves 0, 1 issue, one statement
@@ -85,7 +96,7 @@ __global__ __launch_bounds__(256, 1) void ceiling_kernel(const half8* __restrict
     } else {
         for (int it = 0; it < iters; ++it) {
 #pragma unroll
-            for (int m = 0; m < 48; ++m) c[m & 3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[m & 7], B[(m + m / 8) & 7], c[m & 3], 0, 0, 0);
+            for (int m = 0; m < 48; ++m) c[m & 3] = mfma32<BF>(A[m & 7], B[(m + m / 8) & 7], c[m & 3]);
             if (MODE == 2) {
                 for (int s = 0; s < sleep_n; ++s) __builtin_amdgcn_s_sleep(8);
             }
@@ -203,6 +214,19 @@ static void run_order(const char* name, const half8* dw, const half8* da, int nf
     hipFree(dout); hipFree(sink);
 }
 
+// fp16 -> bf16 bit pattern, round to nearest even (finite inputs; as the trunk's own epilogue rounding)
+static std::vector<_Float16> to_bf16_rne(const std::vector<_Float16>& v) {
+    std::vector<_Float16> o(v.size());
+    for (size_t i = 0; i < v.size(); ++i) {
+        const float f = (float)v[i];
+        unsigned u;
+        memcpy(&u, &f, 4);
+        const unsigned short b = (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+        memcpy(&o[i], &b, 2);
+    }
+    return o;
+}
+
 static std::vector<_Float16> load_or_make(const char* path, size_t n, int kind, unsigned seed) {
     std::vector<_Float16> v(n);
     if (path) {
@@ -224,7 +248,7 @@ static std::vector<_Float16> load_or_make(const char* path, size_t n, int kind, 
     return v;
 }
 
-template <int MODE>
+template <int MODE, int BF = 0>
 static void run(const char* name, const half8* dw, const half8* da, int nfrag, int sleep_n, double seconds) {
     Out* dout; float* sink;
     hipMalloc(&dout, 256 * sizeof(Out)); hipMalloc(&sink, 4);
@@ -238,7 +262,7 @@ static void run(const char* name, const half8* dw, const half8* da, int nfrag, i
             hipMemcpy(wstream + o, dw, nb, hipMemcpyDeviceToDevice);
         }
     }
-    if (lds) hipFuncSetAttribute((const void*)ceiling_kernel<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (lds) hipFuncSetAttribute((const void*)ceiling_kernel<MODE, BF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     const int iters = MODE == 2 ? 2000 : 4000;                    // 48 MFMAs x 32 cyc x 4000 = 6.1 M cycles ~ 3 ms
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     // warm the power state: run for `seconds`, time the second half
@@ -247,7 +271,7 @@ static void run(const char* name, const half8* dw, const half8* da, int nfrag, i
         hipEventRecord(e0);
         int n = 0; float acc = 0;
         do {
-            for (int k = 0; k < 20; ++k) hipLaunchKernelGGL((ceiling_kernel<MODE>), dim3(256), dim3(256), lds, 0, dw, da, nfrag, iters, sleep_n, dout, sink, (const char*)wstream, wstream_b);
+            for (int k = 0; k < 20; ++k) hipLaunchKernelGGL((ceiling_kernel<MODE, BF>), dim3(256), dim3(256), lds, 0, dw, da, nfrag, iters, sleep_n, dout, sink, (const char*)wstream, wstream_b);
             n += 20;
             hipEventRecord(e1); hipEventSynchronize(e1); hipEventElapsedTime(&acc, e0, e1);
         } while (acc < seconds * 500.0);
@@ -297,6 +321,13 @@ int main(int argc, char** argv) {
             run<2>("mfma bursts, sleep 1x", dw, da, nfrag, 1, seconds);
             run<2>("mfma bursts, sleep 2x", dw, da, nfrag, 2, seconds);
             run<2>("mfma bursts, sleep 4x", dw, da, nfrag, 4, seconds);
+        }
+        if (getenv("CEIL_BF16")) {     // the bf16 rows of the same operand data, in the same process, right behind the fp16 rows
+            const std::vector<_Float16> ab = to_bf16_rne(a), wb = to_bf16_rne(w);
+            hipMemcpy(da, ab.data(), n * 2, hipMemcpyHostToDevice); hipMemcpy(dw, wb.data(), n * 2, hipMemcpyHostToDevice);
+            run<0, 1>("bf16: mfma only", dw, da, nfrag, 0, seconds);
+            run<1, 1>("bf16: mfma + 0.75 ds_read_b128 / mfma", dw, da, nfrag, 0, seconds);
+            run<3, 1>("bf16: mfma + lds + weight LDS-DMA stream", dw, da, nfrag, 0, seconds);
         }
         hipFree(da); hipFree(dw);
     }
