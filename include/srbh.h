@@ -118,7 +118,9 @@ int srbh_conv3x3_f16(const srbh_conv3x3_args* a, void* stream);
  * (srbh_pack_conv3x3_b16; gradients need fp32's exponent range), products on v_mfma_f32_32x32x16_bf16.  mask16 != NULL: the output is
  * multiplied by the LeakyReLU derivative taken from the SAVED fp16 activation plane(s) -- chunks mask_chunk0.. of an ACT16 buffer with
  * mask_chunks_total planes: post-activation > 0 ? 1 : 0.2 (torch's leaky_relu backward) -- before the 16-bit / fp32 stores.  No
- * nearest-x2 read in these forms. */
+ * nearest-x2 read in these forms.  bf16 == 2: bf16 input planes and weights as bf16 == 1, but the 16-bit OUTPUT planes are rounded to
+ * fp16 (RNE) -- the last conv5 of the bf16 inference trunk (srbh_rrdbnet_desc.rdb_b16), whose planes leave for conv_body's fp16 operands.
+ * Any other nonzero value means 1.  All 16-bit roundings are round-to-nearest-even; out32 (if also requested) holds the unrounded fp32 values. */
 int srbh_conv3x3_x16(const srbh_conv3x3_args* a, int bf16, const void* mask16, int mask_chunks_total, int mask_chunk0, void* stream);
 int srbh_pack_conv3x3_b16(const float* w_oihw, int cout, int cin, void* packed, void* stream);
 /* the same packs (SR/rrdbnet_arch.py:136-167's conv weights as WPACK16) for MANY convs in ONE launch: table_dev = n descriptors in DEVICE memory;
@@ -241,6 +243,14 @@ int srbh_trunk_wgrad(int num_block, const void* dense_all, size_t dense_stride, 
  * scheduling problem shows up as an error here instead of a hung GPU).  Set SRBH_PERSISTENT=0 to force per-layer launches (the same bits),
  * SRBH_TRUNK_BF16=0 to run the dense blocks on fp16 instead of bf16 operands (see srbh_rrdbnet_desc.rdb_b16). */
 int srbh_rrdbnet_last_status(const void* ws, int B, int H, int W, int want_forward, void* stream);
+
+/* Test / diagnosis accessor: the trunk's fp32 output (the RRDB-level residual stream behind the last RRDB, SR/rrdbnet_arch.py:167 x num_block --
+ * what conv_body reads, before its rounding to fp16) of the LAST srbh_rrdbnet_forward on this workspace, copied to `out` as NHWC32
+ * (B,H,W,64).  The up-sampler tail never writes that stream, so it survives the forward; the two launch forms keep it in different element
+ * orders, and this call undoes the one the forward used: call it with the geometry, num_block and environment (SRBH_PERSISTENT) of that
+ * forward.  `ws` is only read.  The error within the trunk is damped 25 x per RRDB on this stream and not yet hidden under the fp16
+ * roundings of the tail: tests/test_gpu_trunk_parity.py compares it with a rounding-exact CPU emulation. */
+int srbh_rrdbnet_trunk_out(const void* ws, size_t ws_bytes, int num_block, int B, int H, int W, int want_forward, float* out, void* stream);
 
 /* Workgroups per launch of the persistent tail convs (conv_up1 / conv_up2 / conv_hr, SR/rrdbnet_arch.py:234-239) issued by the calling host
  * thread: 0 = one per CU (default), n = at most n.  Each workgroup holds a CU's whole LDS for its walk; a caller that runs the feature

@@ -125,10 +125,11 @@ extern "C" int srbh_conv3x3_f16(const srbh_conv3x3_args* a, void* stream) { retu
 /* The same convolution for the GRADIENT side of the RRDBNet training path (SR/rrdbnet_arch.py:538-592 differentiates the generator):
  * bf16 != 0: the ACT16 input / output planes and the WPACK16 weights hold bf16 (srbh_pack_conv3x3_b16), products on
  * v_mfma_f32_32x32x16_bf16; mask16 != NULL: the output is multiplied by the LeakyReLU derivative taken from the SAVED fp16
- * activation plane(s) mask16[chunk mask_chunk0 ..] (post-activation > 0 ? 1 : 0.2), before the 16-bit / fp32 stores. */
+ * activation plane(s) mask16[chunk mask_chunk0 ..] (post-activation > 0 ? 1 : 0.2), before the 16-bit / fp32 stores.
+ * bf16 == 2: bf16 operands, the 16-bit output rounded to fp16 (the last conv5 of the bf16 inference trunk, conv3x3_trunk_b16(out_f16 = 1)). */
 extern "C" int srbh_conv3x3_x16(const srbh_conv3x3_args* a, int bf16, const void* mask16, int mask_chunks_total, int mask_chunk0,
                                 void* stream) {
-    return conv3x3_impl(a, bf16 ? 1 : 0, mask16, mask_chunks_total, mask_chunk0, stream);
+    return conv3x3_impl(a, bf16 == 2 ? 2 : bf16 ? 1 : 0, mask16, mask_chunks_total, mask_chunk0, stream);
 }
 
 int srbh::conv3x3_trunk_b16(const srbh_conv3x3_args* a, const int out_f16, void* stream) {

@@ -137,6 +137,32 @@ static int device_table(const std::vector<PLayer>& tab, PLayer** out) {
     return SRBH_OK;
 }
 
+// *takes = 1 when a trunk of this geometry runs as the persistent kernel (full 8 x 64 tiles: W == 64, H a multiple of 8, at most one workgroup per
+// CU per image column, the kernel resident with its 160 KiB of LDS): the ONE place that decides it, for ptrunk_run and for whoever has to know
+// afterwards which form wrote a workspace (srbh_rrdbnet_trunk_out).  *ncu_out (optional) = the device's CU count.
+int ptrunk_takes(int num_block, int H, int W, int* takes, int* ncu_out) {
+    *takes = 0;
+    if (W != TILE_W || (H % TILE_H) != 0 || num_block <= 0 || num_block > MAX_BLOCKS) return SRBH_OK;
+    int dev = 0;
+    SRBH_HIP(hipGetDevice(&dev));
+    int ncu = 0;
+    SRBH_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+    if (ncu_out) *ncu_out = ncu;
+    if (H / TILE_H > ncu) return SRBH_OK;
+    constexpr int LDS_B = P_LDS_B;
+    SRBH_ONCE_PER_DEVICE({
+        SRBH_HIP(hipFuncSetAttribute((const void*)ptrunk3_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B));
+        SRBH_HIP(hipFuncSetAttribute((const void*)ptrunk3_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B));
+        SRBH_HIP(hipFuncSetAttribute((const void*)ptrunk3_kernel<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B));
+        SRBH_HIP(hipFuncSetAttribute((const void*)ptrunk3_kernel<0, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B));
+    });
+    int per_cu = 0;
+    SRBH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ptrunk3_kernel<0>, 256, LDS_B));
+    if (per_cu < 1) return SRBH_OK;
+    *takes = 1;
+    return SRBH_OK;
+}
+
 // returns SRBH_OK and sets *used = 1 when the persistent path ran, *used = 0 when the shape is not the kernel's (full 8 x 64 tiles: W == 64,
 // H a multiple of 8, at most one workgroup per CU per image column; the caller then issues the per-layer launch sequence, srbh_rrdbnet.hip)
 // train_stride > 0 = the TRAINING forward (srbh_rrdbnet_trunk_train_forward_persistent): dense0 is RDB 0's buffer of a row of buffers train_stride
@@ -150,24 +176,11 @@ int ptrunk_run(const srbh_rrdbnet_desc* d, void* dense0, void* dense1, float* xr
     *used = 0;
     if (mask && train_stride <= 0) return SRBH_OK;
     SRBH_REQUIRE(!bf16 || (train_stride == 0 && !mask), "ptrunk_run: the bf16 form is the inference forward only");
-    if (W != TILE_W || (H % TILE_H) != 0 || d->num_block <= 0 || d->num_block > MAX_BLOCKS) return SRBH_OK;
-    int dev = 0;
-    SRBH_HIP(hipGetDevice(&dev));
-    int ncu = 0;
-    SRBH_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+    int ncu = 0, takes = 0;
+    if (int rc = ptrunk_takes(d->num_block, H, W, &takes, &ncu)) return rc;
+    if (!takes) return SRBH_OK;
     const int tpi = H / TILE_H;
-    if (tpi > ncu) return SRBH_OK;
     constexpr int LDS_B = P_LDS_B;
-    SRBH_ONCE_PER_DEVICE({
-        SRBH_HIP(hipFuncSetAttribute((const void*)ptrunk3_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B));
-        SRBH_HIP(hipFuncSetAttribute((const void*)ptrunk3_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B));
-        SRBH_HIP(hipFuncSetAttribute((const void*)ptrunk3_kernel<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B));
-        SRBH_HIP(hipFuncSetAttribute((const void*)ptrunk3_kernel<0, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B));
-    });
-    int per_cu = 0;
-    SRBH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ptrunk3_kernel<0>, 256, LDS_B));
-    if (per_cu < 1) return SRBH_OK;
-
     // layer table: the five convs of every RDB in running order (the kernel knows their shapes: four of cout 32, one of cout 64)
     const int nl = d->num_block * 15;
     std::vector<PLayer> tab(nl);

@@ -30,6 +30,25 @@ __global__ __launch_bounds__(256) void poison_on_error_kernel(const int* __restr
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) out[i] = nan;
 }
 
+// The persistent trunk kernel keeps the RRDB-level stream `xrr` in conv5's accumulator ("fragment") order: per image row of 64 pixels x 64
+// channels, float4 number wc * 512 + mb * 256 + g * 64 + lane holds channels mb * 32 + g * 8 + (lane >> 5) * 4 .. + 3 of pixel
+// wc * 32 + (lane & 31) (srbh_ptrunk3_kernel.h, epi64).  This copies such a stream out in pixel order (NHWC); nquads = rows * 1024.
+__global__ __launch_bounds__(256) void trunk_out_pixel_order_kernel(const float* __restrict__ src, float* __restrict__ dst, long nquads) {
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nquads; i += (long)gridDim.x * blockDim.x) {
+        const long row = i >> 10;
+        const int f = (int)(i & 1023);
+        const int lane = f & 63, g = (f >> 6) & 3, mb = (f >> 8) & 1, wc = f >> 9;
+        const int px = wc * 32 + (lane & 31);
+        ((f4*)dst)[row * 1024 + px * 16 + mb * 8 + g * 2 + (lane >> 5)] = ((const f4*)src)[i];
+    }
+}
+
+inline bool persistent_wanted() {
+    const char* env = getenv("SRBH_PERSISTENT");
+    return !(env && env[0] == '0');
+}
+
 WsLayout ws_layout(int B, int H, int W, int want_forward) {
     WsLayout L;
     size_t off = 0;
@@ -92,9 +111,7 @@ extern "C" int srbh_rrdbnet_forward(const srbh_rrdbnet_desc* d, const float* x, 
     int cur = 0;
     int used_persistent = 0;
     {
-        const char* env = getenv("SRBH_PERSISTENT");
-        const bool want = !(env && env[0] == '0');
-        if (want) {
+        if (persistent_wanted()) {
             srbh_rrdbnet_desc dt = *d;
             if (bf16) dt.rdb = d->rdb_b16;
             rc = ptrunk_run(&dt, D[0], D[1], xr, xrr, B, H, W, base + L.aux, (hipStream_t)stream, &used_persistent, &cur, 0, nullptr, 0, bf16);
@@ -179,6 +196,34 @@ extern "C" int srbh_rrdbnet_forward(const srbh_rrdbnet_desc* d, const float* x, 
     a.out32 = out; a.out32_c = d->num_out_ch;
     if ((rc = srbh_conv3x3_f16(&a, stream))) return rc;
     return guard(d->num_out_ch);
+}
+
+/* The trunk's fp32 output -- `xrr` behind the last RRDB, what conv_body's input planes are the fp16 rounding of -- copied out of a workspace
+ * that srbh_rrdbnet_forward has just run on, as NHWC [B][H][W][64].  The tail never touches that stream, so it is still there; its ORDER
+ * depends on the form that ran (per-layer: pixel order; persistent kernel: fragment order per image row), which is decided here exactly as
+ * the forward decides it (SRBH_PERSISTENT read now, ptrunk_takes).  Read only on `ws`.  num_block == 0: conv_first's output. */
+extern "C" int srbh_rrdbnet_trunk_out(const void* ws, size_t ws_bytes, int num_block, int B, int H, int W, int want_forward, float* out,
+                                      void* stream) {
+    SRBH_REQUIRE(ws && out && B > 0 && H > 0 && W > 0 && num_block >= 0, "srbh_rrdbnet_trunk_out: bad arguments");
+    const WsLayout L = ws_layout(B, H, W, want_forward);
+    if (ws_bytes < L.total) {
+        set_error("srbh_rrdbnet_trunk_out: workspace %zu bytes < required %zu", ws_bytes, L.total);
+        return SRBH_ERR_WORKSPACE;
+    }
+    const float* xrr = (const float*)((const char*)ws + L.xrr);
+    const size_t n = (size_t)B * H * W * 64;
+    int fragment = 0;
+    if (persistent_wanted()) {
+        if (int rc = ptrunk_takes(num_block, H, W, &fragment, nullptr)) return rc;
+    }
+    if (!fragment) {
+        SRBH_HIP(hipMemcpyAsync(out, xrr, n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        return SRBH_OK;
+    }
+    const long nquads = (long)(n / 4);       // (W == 64 here: 1024 float4 per image row)
+    hipLaunchKernelGGL(trunk_out_pixel_order_kernel, dim3((unsigned)((nquads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, xrr, out, nquads);
+    SRBH_HIP(hipGetLastError());
+    return SRBH_OK;
 }
 
 extern "C" int srbh_rrdbnet_last_status(const void* ws, int B, int H, int W, int want_forward, void* stream) {

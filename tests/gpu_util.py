@@ -58,3 +58,57 @@ def ref_conv(x, w, b, ups=False, rounded=True):
     if ups:
         x = F.interpolate(x, scale_factor=2, mode="nearest")
     return F.conv2d(x, w, None if b is None else b.double(), 1, 1).float()
+
+
+# ---- 16-bit forms of the conv (srbh_conv3x3_x16): bf16 planes, bf16 packs -------------------------------------------------------
+def b16(t):
+    """round to bf16 (RNE) and back"""
+    return t.to(torch.bfloat16).float()
+
+
+def act16_from_nchw_x16(x, bf16=1, chunks_total=None, chunk0=0, scale=1.0, buf=None):
+    """(B,C,H,W) fp32 cuda, C % 32 == 0 -> planes chunk0.. of a zero-bordered ACT16 buffer as bf16 (or fp16) through
+    srbh_nhwc32_to_act16: the entry the gradient path and the bf16 trunk's tests feed 16-bit planes with"""
+    L = _lib.lib()
+    B, Cc, H, W = x.shape
+    ch = chunks_total or Cc // 32
+    if buf is None:
+        buf = act16_alloc(B, ch, H, W, x.device)
+    src = x.permute(0, 2, 3, 1).contiguous()
+    _lib.check(L.srbh_nhwc32_to_act16(src.data_ptr(), buf.data_ptr(), B, Cc, H, W, ch, chunk0, scale, bf16, _lib.stream_ptr()), "nhwc32_to_act16")
+    torch.cuda.current_stream().synchronize()
+    return buf
+
+
+def act16_raw(buf, B, chunks, H, W, dtype=torch.bfloat16):
+    """the raw 16-bit elements of an ACT16 buffer, borders included: [B][chunks][H+2][W+2][32] view of `dtype`"""
+    return buf.view(dtype)[: B * chunks * (H + 2) * (W + 2) * 32].view(B, chunks, H + 2, W + 2, 32)
+
+
+def act16_planes(buf, B, chunks, H, W, dtype=torch.bfloat16):
+    """the interior of an ACT16 buffer as a (B, 32*chunks, H, W) tensor of `dtype` (the stored bits, no conversion kernel in between)"""
+    raw = act16_raw(buf, B, chunks, H, W, dtype)
+    return raw[:, :, 1:-1, 1:-1].permute(0, 1, 4, 2, 3).reshape(B, chunks * 32, H, W)
+
+
+def border_is_zero(buf, B, chunks, H, W):
+    raw = act16_raw(buf, B, chunks, H, W, torch.int16)
+    return not bool(raw[:, :, 0].any() or raw[:, :, -1].any() or raw[:, :, :, 0].any() or raw[:, :, :, -1].any())
+
+
+def pack_w_b16(w):
+    L = _lib.lib()
+    cout, cin = w.shape[:2]
+    buf = torch.zeros(L.srbh_wpack16_bytes(cout, cin), dtype=torch.uint8, device=w.device)
+    _lib.check(L.srbh_pack_conv3x3_b16(w.contiguous().data_ptr(), cout, cin, buf.data_ptr(), _lib.stream_ptr()), "pack_conv3x3_b16")
+    return buf
+
+
+def run_conv_x16(a, bf16, mask16=None, mask_chunks_total=0, mask_chunk0=0):
+    _lib.check(_lib.lib().srbh_conv3x3_x16(C.byref(a), bf16, None if mask16 is None else mask16.data_ptr(), mask_chunks_total, mask_chunk0,
+                                           _lib.stream_ptr()), "conv3x3_x16")
+
+
+def ref_conv64(x, w, b):
+    """float64 conv of the operands AS GIVEN (round them first), float64 result"""
+    return F.conv2d(x.double(), w.double(), None if b is None else b.double(), 1, 1)
