@@ -113,6 +113,31 @@ typedef struct srbh_conv3x3_args {
 } srbh_conv3x3_args;
 
 int srbh_conv3x3_f16(const srbh_conv3x3_args* a, void* stream);
+
+/* The same convolution on SPLIT fp16 operands (the "f16x2" precision mode of the up-sampler tail, SR/rrdbnet_arch.py:234-239's conv_body /
+ * conv_up1 / conv_up2 / conv_hr): every fp32 value v is carried as hi = rne16(v) and lo' = rne16((v - hi) * 2^11), both fp16, weights
+ * (srbh_pack_conv3x3_f16lo) and activations alike, and the conv is
+ *     C = sum (w_hi * a_lo' + w_lo' * a_hi)     M = sum w_hi * a_hi     y = M + C * 2^-11 + bias      (fp32 accumulators, lo x lo dropped)
+ * followed by `skip` and `lrelu` as above.  `a` describes the hi operands (a->in / a->w) and the outputs, `s` the lo' ones.  64 -> 64
+ * channels (in_chunks == 2, cout == 64), no res1 / res2.  Outputs: out32 (fp32 NHWC, 64 channels); out16 as ACT16 planes = the hi planes of y
+ * with its lo' planes in s->out16_lo (required then); out16 with out16_nhwc = rne16(y) as a dense fp16 NHWC tensor (no lo'). */
+typedef struct srbh_conv3x3_split {
+    const void* in_lo;          /* ACT16 buffer holding the lo' planes of the input, 2 planes from in_lo_chunk0 */
+    int in_lo_chunks_total;
+    int in_lo_chunk0;
+    const void* w_lo;           /* WPACK16 of the weights' lo' parts */
+    void* out16_lo;             /* ACT16 buffer for the lo' planes of the output, or NULL */
+    int out16_lo_chunks_total;
+    int out16_lo_chunk0;
+} srbh_conv3x3_split;
+int srbh_conv3x3_f16x2(const srbh_conv3x3_args* a, const srbh_conv3x3_split* s, void* stream);
+/* OIHW fp32 -> WPACK16 of the lo' parts: rne16((w - rne16(w)) * 2^11) (the hi parts are srbh_pack_conv3x3_f16's pack) */
+int srbh_pack_conv3x3_f16lo(const float* w_oihw, int cout, int cin, void* packed, void* stream);
+/* lo' planes of an fp32 tensor whose hi planes exist: lo' = rne16((v - hi) * 2^11) for the 64 channels of v, hi read from planes
+ * hi_chunk0.. of `hi`, written to planes lo_chunk0.. of `lo` (interior only; borders must be zero already).  v: NHWC fp32 (B,H,W,64), or
+ * (fragment_order != 0, W == 64) the persistent trunk kernel's order of its output stream (see srbh_rrdbnet_trunk_out). */
+int srbh_act16_split_lo(const float* v, int fragment_order, const void* hi, int hi_chunks_total, int hi_chunk0, void* lo, int lo_chunks_total,
+                        int lo_chunk0, int B, int H, int W, void* stream);
 /* The same convolution for the GRADIENT side of the RRDBNet training path (reference SR/rrdbnet_arch.py:538-592 differentiates the
  * generator; round 3, SURVEY 8f-4 second slice).  bf16 != 0: the ACT16 input / output planes and the WPACK16 weights hold bf16
  * (srbh_pack_conv3x3_b16; gradients need fp32's exponent range), products on v_mfma_f32_32x32x16_bf16.  mask16 != NULL: the output is
@@ -131,7 +156,7 @@ typedef struct srbh_pack3x3_desc {
     void* packed;
     const float* bias_src;   /* or NULL */
     float* bias_dst;         /* or NULL */
-    int cout, cin, bf16, pad_;
+    int cout, cin, bf16, pad_;  /* bf16: 0 = fp16 pack, 1 = bf16 pack, 2 = fp16 pack of the lo' parts (srbh_pack_conv3x3_f16lo) */
 } srbh_pack3x3_desc;
 int srbh_pack_conv3x3_many(const srbh_pack3x3_desc* table_dev, int n, long max_elems, void* stream);
 /* NHWC fp32 [B][H][W][C] (C % 32 == 0) * scale -> chunk planes chunk0.. of an ACT16 buffer with chunks_total planes, as fp16 or bf16 */
@@ -182,9 +207,20 @@ typedef struct srbh_rrdbnet_desc {
                                  * fp32 RRDB streams as before, the trunk's output planes rounded to fp16 for conv_body, which with the
                                  * up-sampler tail keeps its fp16 operands.  Environment SRBH_TRUNK_BF16=0 restores the fp16 trunk (A/B).
                                  * The training entry points below always use `rdb`. */
+    int tail_f16x2;             /* 0: the tail convs run on fp16 operands (everything above).  1: the "f16x2" mode -- conv_body, conv_up1,
+                                 * conv_up2 and conv_hr on split fp16 operands (srbh_conv3x3_f16x2), conv_body's lo' planes taken from the
+                                 * trunk's fp32 output stream; needs the lo' packs below and a workspace of
+                                 * srbh_rrdbnet_workspace_bytes_f16x2(); want_forward 0 and 2 only.  The trunk is untouched. */
+    const void* conv_body_lo;   /* srbh_pack_conv3x3_f16lo packs of the tail convs (biases as above); NULL unless tail_f16x2 */
+    const void* conv_up1_lo;
+    const void* conv_up2_lo;
+    const void* conv_hr_lo;
 } srbh_rrdbnet_desc;
 
 size_t srbh_rrdbnet_workspace_bytes(int B, int H, int W, int want_forward);
+/* the workspace of the f16x2 mode (srbh_rrdbnet_desc.tail_f16x2): the layout above with the lo' planes of the up-sampled activations behind
+ * it, so srbh_rrdbnet_last_status / srbh_rrdbnet_trunk_out work on it unchanged and a forward in the default mode may use it too */
+size_t srbh_rrdbnet_workspace_bytes_f16x2(int B, int H, int W, int want_forward);
 /* x: NCHW fp32 (B,num_in_ch,H,W).  out: NHWC32 (B,4H,4W,64) for forward_feature (want_forward=0,
  * no activation after conv_hr -- SR/rrdbnet_arch.py:238) or (B,4H,4W,num_out_ch) for forward
  * (want_forward=1, lrelu(conv_hr) then conv_last -- :221-222).  want_forward=2: forward_feature with `out` a dense fp16 NHWC

@@ -17,7 +17,7 @@ CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(ROOT, "include")
 LIB_PATH = os.path.join(_HERE, "libsrbh.so")
 _DEV_LIB = os.environ.get("SRBH_LIB_PATH")      # developer A/B only (tools/ab_variants.sh): load another build of the same ABI
-SOURCES = ["srbh_conv3x3.hip", "srbh_aux.hip", "srbh_rrdbnet.hip", "srbh_ptrunk.hip", "srbh_trunk_wgrad.hip", "srbh_ptail.hip", "srbh_head.hip", "srbh_head_bwd.hip", "srbh_mosaic.hip", "srbh_loader.hip", "srbh_loss.hip", "srbh_dwconv.hip", "srbh_mbconv.hip", "srbh_pwconv.hip", "srbh_dconv.hip", "srbh_optim.hip"]
+SOURCES = ["srbh_conv3x3.hip", "srbh_aux.hip", "srbh_rrdbnet.hip", "srbh_ptrunk.hip", "srbh_trunk_wgrad.hip", "srbh_ptail.hip", "srbh_ptail_split.hip", "srbh_head.hip", "srbh_head_bwd.hip", "srbh_mosaic.hip", "srbh_loader.hip", "srbh_loss.hip", "srbh_dwconv.hip", "srbh_mbconv.hip", "srbh_pwconv.hip", "srbh_dconv.hip", "srbh_optim.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # NOTE: `-mllvm -amdgpu-mfma-vgpr-form=1` (accumulators in VGPRs: no v_accvgpr copies at K-loop back-edges).  Round 1 saw the
 # first persistent trunk kernel produce non-deterministic garbage with it; round 3 re-ran it on the current kernel (ptrunk3:
@@ -167,6 +167,16 @@ class RRDBNetDesc(C.Structure):
         ("conv_body", ConvW), ("conv_up1", ConvW), ("conv_up2", ConvW), ("conv_hr", ConvW),
         ("conv_last", ConvW), ("num_out_ch", C.c_int),
         ("rdb_b16", C.POINTER(ConvW)),
+        ("tail_f16x2", C.c_int),
+        ("conv_body_lo", C.c_void_p), ("conv_up1_lo", C.c_void_p), ("conv_up2_lo", C.c_void_p), ("conv_hr_lo", C.c_void_p),
+    ]
+
+
+class ConvSplit(C.Structure):
+    _fields_ = [
+        ("in_lo", C.c_void_p), ("in_lo_chunks_total", C.c_int), ("in_lo_chunk0", C.c_int),
+        ("w_lo", C.c_void_p),
+        ("out16_lo", C.c_void_p), ("out16_lo_chunks_total", C.c_int), ("out16_lo_chunk0", C.c_int),
     ]
 
 
@@ -182,6 +192,10 @@ SIGNATURES = {
     "srbh_wpack16_bytes": (_sz, [_i, _i]),
     "srbh_pack_conv3x3_f16": (_i, [_vp, _i, _i, _vp, _vp]),
     "srbh_conv3x3_f16": (_i, [C.POINTER(ConvArgs), _vp]),
+    "srbh_conv3x3_f16x2": (_i, [C.POINTER(ConvArgs), C.POINTER(ConvSplit), _vp]),
+    "srbh_pack_conv3x3_f16lo": (_i, [_vp, _i, _i, _vp, _vp]),
+    "srbh_act16_split_lo": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp]),
+    "srbh_rrdbnet_workspace_bytes_f16x2": (_sz, [_i, _i, _i, _i]),
     "srbh_conv3x3_x16": (_i, [C.POINTER(ConvArgs), _i, _vp, _i, _i, _vp]),
     "srbh_pack_conv3x3_b16": (_i, [_vp, _i, _i, _vp, _vp]),
     "srbh_nhwc32_to_act16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),

@@ -116,7 +116,9 @@ __global__ void pack_w_kernel(const float* __restrict__ w, _Float16* __restrict_
     int oc = mb * 32 + (lane & 31);
     int ic = chunk * 32 + ks * 16 + (lane >> 5) * 8 + j;
     float v = (oc < cout && ic < cin) ? w[((long)oc * cin + ic) * 9 + tap] : 0.f;
-    if constexpr (BF) {          // bf16 (RNE) bits in the 16-bit slot
+    if constexpr (BF == 2) {     // the lo' part of the split-fp16 tail (srbh_ptail_split.hip): what fp16 leaves of v, scaled by 2^11
+        out[idx] = (_Float16)((v - (float)(_Float16)v) * 2048.f);
+    } else if constexpr (BF) {   // bf16 (RNE) bits in the 16-bit slot
         const unsigned u = __builtin_bit_cast(unsigned, v);
         ((unsigned short*)out)[idx] = (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
     } else {
@@ -319,6 +321,16 @@ extern "C" int srbh_pack_conv3x3_b16(const float* w, int cout, int cin, void* pa
     return SRBH_OK;
 }
 
+extern "C" int srbh_pack_conv3x3_f16lo(const float* w, int cout, int cin, void* packed, void* stream) {
+    SRBH_REQUIRE(w && packed && cout > 0 && cin > 0, "srbh_pack_conv3x3_f16lo: bad arguments");
+    int nchunk = (cin + 31) / 32, nmb = (cout + 31) / 32;
+    long total = (long)nchunk * 18 * nmb * 512;
+    hipLaunchKernelGGL(pack_w_kernel<2>, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, w,
+                       (_Float16*)packed, cout, cin, nchunk, nmb);
+    SRBH_HIP(hipGetLastError());
+    return SRBH_OK;
+}
+
 // ---- the same packs for MANY convs in one launch (a generator whose weights move every iteration: 351 forward packs, 345 gradient packs)
 __global__ __launch_bounds__(256) void pack_w_many_kernel(const srbh_pack3x3_desc* __restrict__ table) {
     const srbh_pack3x3_desc d = table[blockIdx.y];
@@ -335,7 +347,9 @@ __global__ __launch_bounds__(256) void pack_w_many_kernel(const srbh_pack3x3_des
     const int chunk = (int)(f / 9);
     const int oc = mb * 32 + (lane & 31), ic = chunk * 32 + ks * 16 + (lane >> 5) * 8 + j;
     const float v = (oc < d.cout && ic < d.cin) ? d.w[((long)oc * d.cin + ic) * 9 + tap] : 0.f;
-    if (d.bf16) {
+    if (d.bf16 == 2) {
+        ((_Float16*)d.packed)[idx] = (_Float16)((v - (float)(_Float16)v) * 2048.f);
+    } else if (d.bf16) {
         const unsigned u = __builtin_bit_cast(unsigned, v);
         ((unsigned short*)d.packed)[idx] = (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
     } else {

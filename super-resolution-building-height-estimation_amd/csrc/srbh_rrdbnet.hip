@@ -14,6 +14,7 @@ namespace {
 
 struct WsLayout {
     size_t d0, d1, feat, xr, xrr, u2, u3, u4, aux, total;
+    size_t u2lo, u3lo;      // f16x2 mode only: the lo' planes of conv_up1's / conv_up2's outputs, BEHIND everything else
     size_t dense_b;
 };
 
@@ -49,7 +50,7 @@ inline bool persistent_wanted() {
     return !(env && env[0] == '0');
 }
 
-WsLayout ws_layout(int B, int H, int W, int want_forward) {
+WsLayout ws_layout(int B, int H, int W, int want_forward, bool f16x2 = false) {
     WsLayout L;
     size_t off = 0;
     L.dense_b = act16_geo(B, 6, H, W).total_b;
@@ -65,6 +66,11 @@ WsLayout ws_layout(int B, int H, int W, int want_forward) {
     if (want_forward == 1) off = align256(off + act16_geo(B, 2, 4 * H, 4 * W).total_b);      // (2 = forward_feature as fp16: no conv_last)
     L.aux = off;   // persistent-trunk layer table, progress counters, error word
     off = align256(off + ptrunk_aux_bytes(B, (H + TILE_H - 1) / TILE_H));
+    L.u2lo = L.u3lo = off;
+    if (f16x2) {      // every offset above is the default layout's: srbh_rrdbnet_last_status / srbh_rrdbnet_trunk_out need not know the mode
+        L.u2lo = off; off = align256(off + act16_geo(B, 2, 2 * H, 2 * W).total_b);
+        L.u3lo = off; off = align256(off + act16_geo(B, 2, 4 * H, 4 * W).total_b);
+    }
     L.total = off;
     return L;
 }
@@ -76,12 +82,21 @@ extern "C" size_t srbh_rrdbnet_workspace_bytes(int B, int H, int W, int want_for
     return ws_layout(B, H, W, want_forward).total;
 }
 
+extern "C" size_t srbh_rrdbnet_workspace_bytes_f16x2(int B, int H, int W, int want_forward) {
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    return ws_layout(B, H, W, want_forward, true).total;
+}
+
 extern "C" int srbh_rrdbnet_forward(const srbh_rrdbnet_desc* d, const float* x, float* out, int B, int H, int W,
                                     int want_forward, void* ws, size_t ws_bytes, void* stream) {
     SRBH_REQUIRE(d && x && out && ws, "srbh_rrdbnet_forward: null pointer");
     SRBH_REQUIRE(B > 0 && H > 0 && W > 0, "srbh_rrdbnet_forward: bad geometry B=%d H=%d W=%d", B, H, W);
     SRBH_REQUIRE(d->num_block >= 0 && d->rdb != nullptr, "srbh_rrdbnet_forward: bad descriptor");
-    const WsLayout L = ws_layout(B, H, W, want_forward);
+    const bool split = d->tail_f16x2 != 0;
+    SRBH_REQUIRE(!split || (d->conv_body_lo && d->conv_up1_lo && d->conv_up2_lo && d->conv_hr_lo),
+                 "srbh_rrdbnet_forward: the f16x2 mode needs the lo' packs of conv_body, conv_up1, conv_up2 and conv_hr");
+    SRBH_REQUIRE(!split || want_forward != 1, "srbh_rrdbnet_forward: the f16x2 mode computes forward_feature only (want_forward 0 or 2)");
+    const WsLayout L = ws_layout(B, H, W, want_forward, split);
     if (ws_bytes < L.total) {
         set_error("srbh_rrdbnet_forward: workspace %zu bytes < required %zu", ws_bytes, L.total);
         return SRBH_ERR_WORKSPACE;
@@ -141,6 +156,58 @@ extern "C" int srbh_rrdbnet_forward(const srbh_rrdbnet_desc* d, const float* x, 
             cur ^= 1;
         }
     }
+    const int* err_word = (const int*)(base + L.aux + ptrunk_err_offset(B, (H + TILE_H - 1) / TILE_H));
+    auto guard = [&](int out_c) -> int {
+        if (!used_persistent) return SRBH_OK;
+        hipLaunchKernelGGL(poison_on_error_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, err_word, out,
+                           (size_t)B * 16 * H * W * out_c);
+        SRBH_HIP(hipGetLastError());
+        return SRBH_OK;
+    };
+    if (split) {
+        // The tail on split fp16 operands (srbh_ptail_split.hip).  hi planes live where the default mode keeps its planes; lo' planes: planes
+        // 2..3 of the dense buffers (x1 / x2 of the last dense block: dead behind the trunk) and the two buffers behind the default layout.
+        // conv_body's hi planes are the trunk's own fp16 output planes, its lo' planes what those leave of the fp32 stream xrr.
+        if ((rc = srbh_act16_split_lo(xrr, used_persistent, D[cur], 6, 0, D[cur], 6, 2, B, H, W, stream))) return rc;
+        srbh_conv3x3_split s;
+        a = srbh_conv3x3_args{};      // conv_body + trunk skip
+        s = srbh_conv3x3_split{};
+        a.in = D[cur]; a.in_chunks_total = 6; a.in_chunk0 = 0; a.in_chunks = 2;
+        s.in_lo = D[cur]; s.in_lo_chunks_total = 6; s.in_lo_chunk0 = 2;
+        a.w = d->conv_body.w; s.w_lo = d->conv_body_lo; a.bias = d->conv_body.bias; a.cout = 64;
+        a.B = B; a.H = H; a.W = W; a.skip = feat;
+        a.out16 = D[cur ^ 1]; a.out16_chunks_total = 6; a.out16_chunk0 = 0;
+        s.out16_lo = D[cur ^ 1]; s.out16_lo_chunks_total = 6; s.out16_lo_chunk0 = 2;
+        if ((rc = srbh_conv3x3_f16x2(&a, &s, stream))) return rc;
+        a = srbh_conv3x3_args{};      // conv_up1 / conv_up2 read through the nearest-x2 index map
+        s = srbh_conv3x3_split{};
+        a.in = D[cur ^ 1]; a.in_chunks_total = 6; a.in_chunk0 = 0; a.in_chunks = 2;
+        s.in_lo = D[cur ^ 1]; s.in_lo_chunks_total = 6; s.in_lo_chunk0 = 2;
+        a.w = d->conv_up1.w; s.w_lo = d->conv_up1_lo; a.bias = d->conv_up1.bias; a.cout = 64;
+        a.B = B; a.H = 2 * H; a.W = 2 * W; a.upsample2x = 1; a.lrelu = 1;
+        a.out16 = U2; a.out16_chunks_total = 2; a.out16_chunk0 = 0;
+        s.out16_lo = base + L.u2lo; s.out16_lo_chunks_total = 2; s.out16_lo_chunk0 = 0;
+        if ((rc = srbh_conv3x3_f16x2(&a, &s, stream))) return rc;
+        a = srbh_conv3x3_args{};
+        s = srbh_conv3x3_split{};
+        a.in = U2; a.in_chunks_total = 2; a.in_chunk0 = 0; a.in_chunks = 2;
+        s.in_lo = base + L.u2lo; s.in_lo_chunks_total = 2; s.in_lo_chunk0 = 0;
+        a.w = d->conv_up2.w; s.w_lo = d->conv_up2_lo; a.bias = d->conv_up2.bias; a.cout = 64;
+        a.B = B; a.H = 4 * H; a.W = 4 * W; a.upsample2x = 1; a.lrelu = 1;
+        a.out16 = U3; a.out16_chunks_total = 2; a.out16_chunk0 = 0;
+        s.out16_lo = base + L.u3lo; s.out16_lo_chunks_total = 2; s.out16_lo_chunk0 = 0;
+        if ((rc = srbh_conv3x3_f16x2(&a, &s, stream))) return rc;
+        a = srbh_conv3x3_args{};      // conv_hr: fp32 NHWC, or rounded once to the fp16 hand-off
+        s = srbh_conv3x3_split{};
+        a.in = U3; a.in_chunks_total = 2; a.in_chunk0 = 0; a.in_chunks = 2;
+        s.in_lo = base + L.u3lo; s.in_lo_chunks_total = 2; s.in_lo_chunk0 = 0;
+        a.w = d->conv_hr.w; s.w_lo = d->conv_hr_lo; a.bias = d->conv_hr.bias; a.cout = 64;
+        a.B = B; a.H = 4 * H; a.W = 4 * W;
+        if (want_forward == 2) { a.out16 = out; a.out16_chunks_total = 2; a.out16_chunk0 = 0; a.out16_nhwc = 1; }
+        else { a.out32 = out; a.out32_c = 64; }
+        if ((rc = srbh_conv3x3_f16x2(&a, &s, stream))) return rc;
+        return guard(want_forward == 2 ? 32 : 64);
+    }
     // conv_body + trunk skip
     a = srbh_conv3x3_args{};
     a.in = D[cur]; a.in_chunks_total = 6; a.in_chunk0 = 0; a.in_chunks = 2;
@@ -166,14 +233,6 @@ extern "C" int srbh_rrdbnet_forward(const srbh_rrdbnet_desc* d, const float* x, 
     a.in = U3; a.in_chunks_total = 2; a.in_chunk0 = 0; a.in_chunks = 2;
     a.w = d->conv_hr.w; a.bias = d->conv_hr.bias; a.cout = 64;
     a.B = B; a.H = 4 * H; a.W = 4 * W;
-    const int* err_word = (const int*)(base + L.aux + ptrunk_err_offset(B, (H + TILE_H - 1) / TILE_H));
-    auto guard = [&](int out_c) -> int {
-        if (!used_persistent) return SRBH_OK;
-        hipLaunchKernelGGL(poison_on_error_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, err_word, out,
-                           (size_t)B * 16 * H * W * out_c);
-        SRBH_HIP(hipGetLastError());
-        return SRBH_OK;
-    };
     if (want_forward == 2) {      // forward_feature as a dense fp16 NHWC tensor (the 16-bit head kernels stage it verbatim)
         a.out16 = out; a.out16_chunks_total = 2; a.out16_chunk0 = 0; a.out16_nhwc = 1;
         if ((rc = srbh_conv3x3_f16(&a, stream))) return rc;

@@ -726,7 +726,9 @@ class _PredictGraph:
         from . import hrfuse as _H
         k = tuple((t._version, getattr(t, "_srbh_gen", 0), t.data_ptr())
                   for m in (net_hr, model) for t in list(m.parameters()) + list(m.buffers()))
-        return (k, batch, str(dev), wcache.gen(), _H._HEAD_PRECISION["mode"])
+        # (the feature extractor's precision mode selects other kernels and another workspace: a graph captured in one mode is not replayed in another)
+        prec = net_hr._precision() if hasattr(net_hr, "_precision") else None
+        return (k, batch, str(dev), wcache.gen(), _H._HEAD_PRECISION["mode"], prec)
 
     def reset(self):
         """forget an encoder pass launched ahead (a city loop that ended early): the next call stages its own"""

@@ -178,8 +178,9 @@ class RRDBNet(nn.Module):
         if all(t.device == dev and t.dtype == torch.float32 and t.is_contiguous() for t in params):
             return self._pack_in_place(dev, convs, params)
         n_rdb = num_block * 15
+        tail = convs[n_rdb:n_rdb + 4]      # conv_body, conv_up1, conv_up2, conv_hr: their lo' packs (precision "f16x2") behind everything
         # the dense-block convs twice: fp16 packs (training paths, SRBH_TRUNK_BF16=0) and bf16 packs (the inference trunk), behind all convs
-        sizes = [L.srbh_wpack16_bytes(c.out_channels, c.in_channels) for c in convs + convs[:n_rdb]]
+        sizes = [L.srbh_wpack16_bytes(c.out_channels, c.in_channels) for c in convs + convs[:n_rdb] + tail]
         offs, tot = [], 0
         for s in sizes:
             offs.append(tot)
@@ -202,6 +203,9 @@ class RRDBNet(nn.Module):
         for i, (c, w) in enumerate(zip(convs[:n_rdb], keep)):
             _lib.check(L.srbh_pack_conv3x3_b16(w.data_ptr(), c.out_channels, c.in_channels, wbuf.data_ptr() + offs[len(convs) + i], st),
                        "pack_conv3x3_b16")
+        for j, c in enumerate(tail):
+            _lib.check(L.srbh_pack_conv3x3_f16lo(keep[n_rdb + j].data_ptr(), c.out_channels, c.in_channels,
+                                                 wbuf.data_ptr() + offs[len(convs) + n_rdb + j], st), "pack_conv3x3_f16lo")
         rdb_arr = (_lib.ConvW * max(n_rdb, 1))()
         rdb_b16 = (_lib.ConvW * max(n_rdb, 1))()
         for i in range(n_rdb):
@@ -222,6 +226,8 @@ class RRDBNet(nn.Module):
             setattr(d, name, cw)
         d.num_out_ch = num_out_ch
         d.rdb_b16 = C.cast(rdb_b16, C.POINTER(_lib.ConvW)) if n_rdb else None
+        for j, name in enumerate(("conv_body_lo", "conv_up1_lo", "conv_up2_lo", "conv_hr_lo")):
+            setattr(d, name, wbuf.data_ptr() + offs[len(convs) + n_rdb + j])
         torch.cuda.current_stream().synchronize()  # `keep` temporaries may be freed after this
         return (wbuf, bbuf, cf_w, cf_b, rdb_arr, rdb_b16), d
 
@@ -238,8 +244,10 @@ class RRDBNet(nn.Module):
             num_in_ch, num_out_ch, num_feat, num_block, num_grow_ch = self._geom
             n_rdb = num_block * 15
             # the dense-block convs twice: fp16 packs (training paths, SRBH_TRUNK_BF16=0) and bf16 packs (the inference trunk), behind all
-            # convs; both are rewritten by the same launch, so a weight update reaches either form
-            sizes = [L.srbh_wpack16_bytes(c.out_channels, c.in_channels) for c in convs + convs[:n_rdb]]
+            # convs; behind those the lo' packs of the four tail convs (precision "f16x2"); all are rewritten by the same launch, so a
+            # weight update reaches every form
+            tail = convs[n_rdb:n_rdb + 4]
+            sizes = [L.srbh_wpack16_bytes(c.out_channels, c.in_channels) for c in convs + convs[:n_rdb] + tail]
             offs, tot = [], 0
             for sz in sizes:
                 offs.append(tot)
@@ -253,12 +261,15 @@ class RRDBNet(nn.Module):
                 bo += bp
             desc_t = np.dtype([("w", np.uint64), ("packed", np.uint64), ("bias_src", np.uint64), ("bias_dst", np.uint64), ("cout", np.int32), ("cin", np.int32),
                                ("bf16", np.int32), ("pad", np.int32)])
-            tab = np.zeros(len(convs) + n_rdb, dtype=desc_t)
+            tab = np.zeros(len(convs) + n_rdb + len(tail), dtype=desc_t)
             for i, c in enumerate(convs):
                 tab[i] = (c.weight.data_ptr(), wbuf.data_ptr() + offs[i], 0 if c.bias is None else c.bias.data_ptr(),
                           0 if c.bias is None else bbuf.data_ptr() + 4 * boffs[i], c.out_channels, c.in_channels, 0, 0)
             for i, c in enumerate(convs[:n_rdb]):      # (bias table: written by the fp16 entry)
                 tab[len(convs) + i] = (c.weight.data_ptr(), wbuf.data_ptr() + offs[len(convs) + i], 0, 0, c.out_channels, c.in_channels, 1, 0)
+            for j, c in enumerate(tail):
+                k = len(convs) + n_rdb + j
+                tab[k] = (c.weight.data_ptr(), wbuf.data_ptr() + offs[k], 0, 0, c.out_channels, c.in_channels, 2, 0)
             table = torch.from_numpy(tab.view(np.uint8).copy()).to(dev)
             rdb_arr = (_lib.ConvW * max(n_rdb, 1))()
             rdb_b16 = (_lib.ConvW * max(n_rdb, 1))()
@@ -277,6 +288,8 @@ class RRDBNet(nn.Module):
                 setattr(d, name, _lib.ConvW(wbuf.data_ptr() + offs[n_rdb + j], bbuf.data_ptr() + 4 * boffs[n_rdb + j]))
             d.num_out_ch = num_out_ch
             d.rdb_b16 = C.cast(rdb_b16, C.POINTER(_lib.ConvW)) if n_rdb else None
+            for j, name in enumerate(("conv_body_lo", "conv_up1_lo", "conv_up2_lo", "conv_hr_lo")):
+                setattr(d, name, wbuf.data_ptr() + offs[len(convs) + n_rdb + j])
             plan = self.__dict__["_pack_plan"] = {"key": key, "bufs": (wbuf, bbuf, table, rdb_arr, rdb_b16, params), "desc": d, "table": table,
                                                   "n": len(tab), "max_elems": max(sizes) // 2}
         _lib.check(L.srbh_pack_conv3x3_many(plan["table"].data_ptr(), plan["n"], plan["max_elems"], _lib.stream_ptr()), "pack_conv3x3_many")
@@ -300,12 +313,13 @@ class RRDBNet(nn.Module):
             wcache.keep(self._packed)
             return self._packed[1], self._packed[2]
 
-    def _workspace(self, B, H, W, want_forward, device):
-        key = (B, H, W, int(want_forward), device)
+    def _workspace(self, B, H, W, want_forward, device, split=False):
+        key = (B, H, W, int(want_forward), device) + (("f16x2",) if split else ())
         pins = self.__dict__.setdefault("_ws_pins", {})
         ws = self._workspaces.get(key)
         if ws is None:
-            n = _lib.lib().srbh_rrdbnet_workspace_bytes(B, H, W, int(want_forward))
+            size_of = _lib.lib().srbh_rrdbnet_workspace_bytes_f16x2 if split else _lib.lib().srbh_rrdbnet_workspace_bytes
+            n = size_of(B, H, W, int(want_forward))
             ws = torch.zeros(n, dtype=torch.uint8, device=device)  # zero borders are an invariant of the kernels
             self._workspaces[key] = ws
             total = sum(t.numel() for t in self._workspaces.values())
@@ -368,6 +382,10 @@ class RRDBNet(nn.Module):
                     out.copy_(r)
                     return out
                 return r
+        split = self._tail_split()
+        if split and want_forward:
+            raise NotImplementedError('RRDBNet.forward (the x4 image through conv_last) is not available with precision = "f16x2": the mode '
+                                      'covers forward_feature; use precision "f16" or "f32" for forward')
         if self.scale == 2:
             x = pixel_unshuffle(x, 2)
         elif self.scale == 1:
@@ -382,8 +400,10 @@ class RRDBNet(nn.Module):
                 bufs, desc = self._pack(x.device)
                 self._packed = (key, bufs, desc)
             desc = self._packed[2]
+            if split:                                    # the same packs and pointers, the mode switched on: one descriptor per mode, cached with the packs
+                desc = self._split_desc(desc)
             wcache.keep(self._packed)                    # (a capturing graph owns the layer table + packed weights it bakes in)
-            ws = self._workspace(B, H, W, want_forward, x.device)
+            ws = self._workspace(B, H, W, want_forward, x.device, split)
             cout = self._geom[1] if want_forward else 64
             odt = torch.float16 if h16 else torch.float32
             if out is None:
@@ -402,7 +422,7 @@ class RRDBNet(nn.Module):
         """Synchronise and raise if the last forward's persistent trunk kernel reported a timeout (tests / smoke / bench
         call this outside timed regions; the kernels themselves never hang: every spin is bounded)."""
         L = _lib.lib()
-        for (B, H, W, wf, dev), ws in self._workspaces.items():
+        for (B, H, W, wf, dev, *_mode), ws in self._workspaces.items():
             with torch.cuda.device(dev):
                 _lib.check(L.srbh_rrdbnet_last_status(ws.data_ptr(), B, H, W, wf, _lib.stream_ptr()), "rrdbnet_last_status")
 
@@ -477,9 +497,26 @@ class RRDBNet(nn.Module):
         conv(self.conv_last, hr, 64, 64, out)
         return out.permute(0, 3, 1, 2)
 
-    def _use_strict(self):
+    def _precision(self):
         import os
-        return getattr(self, "precision", os.environ.get("SRBH_TRUNK_PRECISION", "f16")) in ("f32", "fp32", "strict")
+        return getattr(self, "precision", os.environ.get("SRBH_TRUNK_PRECISION", "f16"))
+
+    def _use_strict(self):
+        return self._precision() in ("f32", "fp32", "strict")
+
+    def _tail_split(self):
+        """precision "f16x2": the bf16 trunk as it is, the four 64 -> 64 convs behind it on split fp16 operands (csrc/srbh_ptail_split.hip)"""
+        return self._precision() == "f16x2"
+
+    def _split_desc(self, desc):
+        """the packed descriptor with tail_f16x2 set; a copy that lives as long as the packs it points into"""
+        memo = self.__dict__.get("_split_desc_memo")
+        if memo is None or memo[0] is not desc:
+            d2 = _lib.RRDBNetDesc()
+            C.memmove(C.byref(d2), C.byref(desc), C.sizeof(_lib.RRDBNetDesc))
+            d2.tail_f16x2 = 1
+            memo = self.__dict__["_split_desc_memo"] = (desc, d2)
+        return memo[1]
 
     def forward(self, x):
         """reference SR/rrdbnet_arch.py:208-223 -> (B,num_out_ch,4H,4W), channels_last strides."""
