@@ -17,31 +17,22 @@
 //  It is 0.4 % faster on forward_feature and 0.6 % slower in the tiled prediction (profiles/r06ah_ab_ptail_pipe.txt): with the phases
 //  overlapped the launch draws more power at once and the package clocks down -- the tail convs are energy-bound like the trunk,
 //  not latency-bound.  Not kept.)
-#include <stdlib.h>
-#include "srbh_conv3x3_kernel.h"
+#include "srbh_ptail_kernel.h"
 
 namespace {
 using namespace srbh;
 using namespace srbh_k;
 
 struct TParams {
-    const char* in;             // first input plane (ACT16)
-    long in_img_b;
-    int in_plane_b, in_row_b;
+    In16 in;                    // first input plane
     const char* w;              // WPACK16, 2 chunks x 36 KiB
     const float* bias;
     int H, W;                   // OUTPUT geometry
     int tiles_x, tiles_per_img, ntiles, tiles_per_wg;
     int lrelu;
-    char* out16;                // ACT16 output (2 planes) or nullptr
-    long out16_img_b;
-    int out16_plane_b, out16_row_b;
-    int out16_pix_b, out16_border;   // ACT16: 64-byte pixel records behind a 1-pixel border; NHWC16 (srbh_conv3x3_args::out16_nhwc): dense
-                                     // fp16 [B][H][W][C] records of out16_pix_b bytes, no border, "plane" = 64 bytes (the next 32 channels)
+    Out16 out16;                // ACT16 (2 planes) or NHWC16 output, or none
     float* out32;               // fp32 NHWC (64 channels) output or nullptr
 };
-
-constexpr int W_RES_B = 2 * 36 * 1024;   // resident weights of both chunks
 
 template <int UPS>
 __global__ __launch_bounds__(256, 1) void ptail_kernel(const TParams p) {
@@ -63,7 +54,7 @@ __global__ __launch_bounds__(256, 1) void ptail_kernel(const TParams p) {
         const int trow = u / (G::COLS * 4);
         const int rem = u - trow * (G::COLS * 4);
         const int pc = rem >> 2, ps = rem & 3;
-        goff[j] = trow * p.in_row_b + pc * PIX_B + ((ps ^ ((pc >> 2) & 3)) << 4);
+        goff[j] = trow * p.in.row_b + pc * PIX_B + ((ps ^ ((pc >> 2) & 3)) << 4);
     }
     const unsigned long long tail_mask = __builtin_amdgcn_ballot_w64((G::NJ - 1) * 256 + tid < G::UNITS);
     int aoff[3][2];
@@ -75,35 +66,20 @@ __global__ __launch_bounds__(256, 1) void ptail_kernel(const TParams p) {
             aoff[dx][ks] = wr * (UPS ? 2 : 4) * G::ROW_B + pc * PIX_B + (((ks * 2 + hi) ^ ((pc >> 2) & 3)) << 4);
     }
 
-    // 16 B per lane LDS-DMA under an explicit EXEC mask (see srbh_ptrunk.hip)
-    auto dma16 = [&](const char* gaddr, const unsigned lds_off_v, const unsigned long long mask) {
-        unsigned long long sv;
-        const unsigned lds_off = __builtin_amdgcn_readfirstlane(lds_off_v);
-        asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, %1\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                     "global_load_lds_dwordx4 %3, off\n\ts_mov_b64 exec, %0"
-                     : "=&s"(sv) : "s"(mask), "s"(lds_off), "v"(gaddr) : "memory", "m0");
-    };
-    auto tile_origin = [&](int t, int& img, int& Y0, int& X0) {
-        img = t / p.tiles_per_img;
-        const int trem = t - img * p.tiles_per_img;
-        const int ty = trem / p.tiles_x;
-        Y0 = ty * TILE_H;
-        X0 = (trem - ty * p.tiles_x) * TILE_W;
-    };
     auto stage_inputs = [&](int t) {
         int img, Y0, X0;
-        tile_origin(t, img, Y0, X0);
-        const char* src0 = p.in + (long)img * p.in_img_b + (long)(UPS ? (Y0 >> 1) : Y0) * p.in_row_b + (UPS ? (X0 >> 1) : X0) * PIX_B;
+        tile_origin(t, p.tiles_per_img, p.tiles_x, img, Y0, X0);
+        const char* src0 = p.in.base + (long)img * p.in.img_b + (long)(UPS ? (Y0 >> 1) : Y0) * p.in.row_b + (UPS ? (X0 >> 1) : X0) * PIX_B;
 #pragma unroll
         for (int c = 0; c < 2; ++c)
 #pragma unroll
             for (int j = 0; j < G::NJ; ++j)
-                dma16(src0 + (long)c * p.in_plane_b + goff[j], W_RES_B + c * IN_EX + (j * 256 + wave * 64) * 16,
+                dma16(src0 + (long)c * p.in.plane_b + goff[j], TAIL_W_B + c * IN_EX + (j * 256 + wave * 64) * 16,
                       j < G::NJ - 1 ? ~0ull : tail_mask);
     };
 
     // epilogue stores per wave and tile when every tile is full (no store predicated off): see the wait at the top of the tile loop
-    const int nst = ((p.H & (TILE_H - 1)) == 0 && (p.W & (TILE_W - 1)) == 0) ? (p.out32 ? 32 : 0) + (p.out16 ? 16 : 0) : 0;
+    const int nst = ((p.H & (TILE_H - 1)) == 0 && (p.W & (TILE_W - 1)) == 0) ? (p.out32 ? 32 : 0) + (p.out16.base ? 16 : 0) : 0;
     const int t0 = blockIdx.x * p.tiles_per_wg;
     const int t1 = (t0 + p.tiles_per_wg < p.ntiles) ? t0 + p.tiles_per_wg : p.ntiles;
     if (t0 >= t1) return;
@@ -120,7 +96,7 @@ __global__ __launch_bounds__(256, 1) void ptail_kernel(const TParams p) {
 
     for (int t = t0; t < t1; ++t) {
         int img, Y0, X0;
-        tile_origin(t, img, Y0, X0);
+        tile_origin(t, p.tiles_per_img, p.tiles_x, img, Y0, X0);
         // this tile's inputs (and, first time, the weights) landed ...  From the second tile on the only operations YOUNGER than that DMA are the
         // previous tile's epilogue stores (issued behind stage_inputs): full tiles issue a fixed number of them per wave -- 32 (fp32 output) and /
         // or 16 (16-bit output) -- so the wait leaves exactly those in flight instead of waiting for their acknowledgement as well
@@ -142,7 +118,7 @@ __global__ __launch_bounds__(256, 1) void ptail_kernel(const TParams p) {
         auto load_group = [&](int q, int set) {   // q = chunk * 6 + (ks * 3 + dx)
             const int c = q / 6, g = q - c * 6;
             const int ks = g / 3, dx = g - ks * 3;
-            const char* sbi = smem + W_RES_B + c * IN_EX;
+            const char* sbi = smem + TAIL_W_B + c * IN_EX;
             const char* sbw = smem + c * (36 * 1024) + lane * 16;
 #pragma unroll
             for (int r = 0; r < G::NP; ++r) P[set][r] = *(const half8*)(sbi + aoff[dx][ks] + r * G::ROW_B);
@@ -209,16 +185,10 @@ __global__ __launch_bounds__(256, 1) void ptail_kernel(const TParams p) {
                     hp[g][0] = u.x;
                     hp[g][1] = u.y;
                 }
-                if (p.out16) {
+                if (p.out16.base) {
 #pragma unroll
                     for (int m = 0; m < 2; ++m) {
-                        auto s0 = __builtin_amdgcn_permlane32_swap(hp[2 * m][0], hp[2 * m + 1][0], false, false);
-                        auto s1 = __builtin_amdgcn_permlane32_swap(hp[2 * m][1], hp[2 * m + 1][1], false, false);
-                        typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
-                        const uintx4 raw = {s0[0], s1[0], s0[1], s1[1]};
-                        if (valid)
-                            *(uintx4*)(p.out16 + (long)img * p.out16_img_b + (long)mb * p.out16_plane_b + (long)(Y + p.out16_border) * p.out16_row_b +
-                                       (X + p.out16_border) * p.out16_pix_b + m * 32 + hi * 16) = raw;
+                        store16_pair(p.out16, valid, img, mb, Y, X, m, hi, hp[2 * m], hp[2 * m + 1]);
                     }
                 }
             }
@@ -230,26 +200,12 @@ thread_local int g_ptail_wgs_cap = 0;      // srbh_ptail_wgs_cap: workgroups per
 
 template <int UPS>
 int launch(const TParams& p0, hipStream_t stream) {
-    constexpr int LDS_B = W_RES_B + 2 * TileGeo<UPS>::UNITS * 16;
-    static_assert(LDS_B <= 163840, "resident weights + both input chunks must fit the 160 KiB LDS");
-    SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)ptail_kernel<UPS>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B)));
-    static int ncu_of[64] = {0};   // CU count per device (queried once each)
-    int dev = 0;
-    SRBH_HIP(hipGetDevice(&dev));
-    if (!ncu_of[dev & 63]) SRBH_HIP(hipDeviceGetAttribute(&ncu_of[dev & 63], hipDeviceAttributeMultiprocessorCount, dev));
-    int ncu = ncu_of[dev & 63];
-    // SRBH_PTAIL_WGS (harness knob, like SRBH_PT_IMAGES): fewer workgroups than CUs -- this kernel holds a whole CU's LDS per workgroup for
-    // its entire walk, so a full grid lets no kernel of another stream in while it runs
-    if (g_ptail_wgs_cap > 0 && g_ptail_wgs_cap < ncu) ncu = g_ptail_wgs_cap;
-    if (const char* we = getenv("SRBH_PTAIL_WGS")) {          // (developer A/B aid: overrides the caller's cap)
-        const int cap = atoi(we);
-        if (cap > 0 && cap < ncu_of[dev & 63]) ncu = cap;
-    }
+    static_assert(TAIL_LDS_B<UPS> <= 163840, "resident weights + both input chunks must fit the 160 KiB LDS");
+    SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)ptail_kernel<UPS>, hipFuncAttributeMaxDynamicSharedMemorySize, TAIL_LDS_B<UPS>)));
     TParams p = p0;
-    const int nwg = p.ntiles < ncu ? p.ntiles : ncu;
-    p.tiles_per_wg = (p.ntiles + nwg - 1) / nwg;
-    const int grid = (p.ntiles + p.tiles_per_wg - 1) / p.tiles_per_wg;
-    hipLaunchKernelGGL(ptail_kernel<UPS>, dim3(grid), dim3(256), LDS_B, stream, p);
+    int grid = 0;
+    if (const int rc = tail_grid(p.ntiles, &p.tiles_per_wg, &grid)) return rc;
+    hipLaunchKernelGGL(ptail_kernel<UPS>, dim3(grid), dim3(256), TAIL_LDS_B<UPS>, stream, p);
     SRBH_HIP(hipGetLastError());
     return SRBH_OK;
 }
@@ -267,6 +223,8 @@ extern "C" int srbh_ptail_wgs_cap(int cap) {
 
 namespace srbh {
 
+int ptail_wgs_cap() { return g_ptail_wgs_cap; }
+
 // *used = 1 when the persistent form ran (64 -> 64 channels, no residual / skip epilogue), 0 when the caller must launch
 // the per-tile kernel
 int ptail_run(const srbh_conv3x3_args* a, hipStream_t stream, int* used) {
@@ -278,13 +236,8 @@ int ptail_run(const srbh_conv3x3_args* a, hipStream_t stream, int* used) {
     const int tiles_x = (a->W + TILE_W - 1) / TILE_W, tiles_y = (a->H + TILE_H - 1) / TILE_H;
     if (a->out16_nhwc && (!a->out16 || a->out32)) return SRBH_OK;
     if ((long)tiles_x * tiles_y * a->B < 512 && !a->out16_nhwc) return SRBH_OK;   // too few tiles per CU to amortise the resident weights (the NHWC16 store exists only here)
-    const int inH = a->upsample2x ? a->H / 2 : a->H, inW = a->upsample2x ? a->W / 2 : a->W;
-    const Act16Geo gi = act16_geo(a->B, a->in_chunks_total, inH, inW);
     TParams p{};
-    p.in = (const char*)a->in + (long)a->in_chunk0 * gi.plane_b;
-    p.in_img_b = gi.img_b;
-    p.in_plane_b = gi.plane_b;
-    p.in_row_b = gi.row_b;
+    p.in = tail_in16(a, a->in, a->in_chunks_total, a->in_chunk0);
     p.w = (const char*)a->w;
     p.bias = a->bias;
     p.H = a->H;
@@ -293,23 +246,7 @@ int ptail_run(const srbh_conv3x3_args* a, hipStream_t stream, int* used) {
     p.tiles_per_img = tiles_x * tiles_y;
     p.ntiles = p.tiles_per_img * a->B;
     p.lrelu = a->lrelu;
-    if (a->out16 && a->out16_nhwc) {
-        const int C = a->out16_chunks_total * 32;
-        p.out16 = (char*)a->out16 + (long)a->out16_chunk0 * 64;
-        p.out16_pix_b = C * 2;
-        p.out16_row_b = a->W * C * 2;
-        p.out16_img_b = (long)a->H * a->W * C * 2;
-        p.out16_plane_b = 64;
-        p.out16_border = 0;
-    } else if (a->out16) {
-        const Act16Geo go = act16_geo(a->B, a->out16_chunks_total, a->H, a->W);
-        p.out16_pix_b = PIX_B;
-        p.out16_border = 1;
-        p.out16 = (char*)a->out16 + (long)a->out16_chunk0 * go.plane_b;
-        p.out16_img_b = go.img_b;
-        p.out16_plane_b = go.plane_b;
-        p.out16_row_b = go.row_b;
-    }
+    p.out16 = tail_out16(a, a->out16, a->out16_chunks_total, a->out16_chunk0);
     p.out32 = a->out32;
     const int rc = a->upsample2x ? launch<1>(p, stream) : launch<0>(p, stream);
     if (rc == SRBH_OK) *used = 1;

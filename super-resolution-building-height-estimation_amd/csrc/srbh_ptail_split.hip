@@ -16,8 +16,7 @@
 // i.e. per tile 144 KiB of weights (L2 hits: every workgroup reads the same two packs) and 168 KiB of input go through the LDS-DMA, each
 // behind a full wait + barrier.  Every wait is s_waitcnt vmcnt(0): no counted waits, so none of their hazards.
 // A workgroup walks a contiguous range of tiles; a launch with fewer tiles than CUs (conv_body at B x 64 x 64) runs one tile per workgroup.
-#include <stdlib.h>
-#include "srbh_conv3x3_kernel.h"
+#include "srbh_ptail_kernel.h"
 
 namespace {
 using namespace srbh;
@@ -42,7 +41,6 @@ struct SParams {
     float* out32;               // fp32 NHWC (64 channels) output or nullptr
 };
 
-constexpr int W_RES_B = 2 * 36 * 1024;
 constexpr float LO_SCALE = 2048.f, LO_UNSCALE = 1.f / 2048.f;
 
 template <int UPS>
@@ -77,30 +75,15 @@ __global__ __launch_bounds__(256, 1) void ptail_split_kernel(const SParams p) {
             aoff[dx][ks] = wr * (UPS ? 2 : 4) * G::ROW_B + pc * PIX_B + (((ks * 2 + hi) ^ ((pc >> 2) & 3)) << 4);
     }
 
-    // 16 B per lane LDS-DMA under an explicit EXEC mask (see srbh_ptrunk.hip)
-    auto dma16 = [&](const char* gaddr, const unsigned lds_off_v, const unsigned long long mask) {
-        unsigned long long sv;
-        const unsigned lds_off = __builtin_amdgcn_readfirstlane(lds_off_v);
-        asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, %1\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                     "global_load_lds_dwordx4 %3, off\n\ts_mov_b64 exec, %0"
-                     : "=&s"(sv) : "s"(mask), "s"(lds_off), "v"(gaddr) : "memory", "m0");
-    };
-    auto tile_origin = [&](int t, int& img, int& Y0, int& X0) {
-        img = t / p.tiles_per_img;
-        const int trem = t - img * p.tiles_per_img;
-        const int ty = trem / p.tiles_x;
-        Y0 = ty * TILE_H;
-        X0 = (trem - ty * p.tiles_x) * TILE_W;
-    };
     auto stage_inputs = [&](int t, const char* base, long img_b) {
         int img, Y0, X0;
-        tile_origin(t, img, Y0, X0);
+        tile_origin(t, p.tiles_per_img, p.tiles_x, img, Y0, X0);
         const char* src0 = base + (long)img * img_b + (long)(UPS ? (Y0 >> 1) : Y0) * p.in_row_b + (UPS ? (X0 >> 1) : X0) * PIX_B;
 #pragma unroll
         for (int c = 0; c < 2; ++c)
 #pragma unroll
             for (int j = 0; j < G::NJ; ++j)
-                dma16(src0 + (long)c * p.in_plane_b + goff[j], W_RES_B + c * IN_EX + (j * 256 + wave * 64) * 16,
+                dma16(src0 + (long)c * p.in_plane_b + goff[j], TAIL_W_B + c * IN_EX + (j * 256 + wave * 64) * 16,
                       j < G::NJ - 1 ? ~0ull : tail_mask);
     };
     auto stage_weights = [&](const char* w) {     // 72 fragments of 1 KiB, 18 per wave
@@ -108,6 +91,8 @@ __global__ __launch_bounds__(256, 1) void ptail_split_kernel(const SParams p) {
         for (int k = 0; k < 18; ++k) dma16(w + (wave + 4 * k) * 1024 + lane * 16, (wave + 4 * k) * 1024, ~0ull);
     };
 
+    const Out16 out_hi{p.out_hi, p.out_hi_img_b, p.out_plane_b, p.out_row_b, p.out_pix_b, p.out_border};
+    const Out16 out_lo{p.out_lo, p.out_lo_img_b, p.out_plane_b, p.out_row_b, p.out_pix_b, p.out_border};
     const int t0 = blockIdx.x * p.tiles_per_wg;
     const int t1 = (t0 + p.tiles_per_wg < p.ntiles) ? t0 + p.tiles_per_wg : p.ntiles;
     if (t0 >= t1) return;
@@ -122,7 +107,7 @@ __global__ __launch_bounds__(256, 1) void ptail_split_kernel(const SParams p) {
 
     for (int t = t0; t < t1; ++t) {
         int img, Y0, X0;
-        tile_origin(t, img, Y0, X0);
+        tile_origin(t, p.tiles_per_img, p.tiles_x, img, Y0, X0);
         floatx16 acc[CB][4];
 #pragma unroll
         for (int mb = 0; mb < CB; ++mb)
@@ -152,7 +137,7 @@ __global__ __launch_bounds__(256, 1) void ptail_split_kernel(const SParams p) {
             auto load_group = [&](int q, int set) {   // q = chunk * 6 + (ks * 3 + dx)
                 const int c = q / 6, g = q - c * 6;
                 const int ks = g / 3, dx = g - ks * 3;
-                const char* sbi = smem + W_RES_B + c * IN_EX;
+                const char* sbi = smem + TAIL_W_B + c * IN_EX;
                 const char* sbw = smem + c * (36 * 1024) + lane * 16;
 #pragma unroll
                 for (int r = 0; r < G::NP; ++r) P[set][r] = *(const half8*)(sbi + aoff[dx][ks] + r * G::ROW_B);
@@ -228,28 +213,13 @@ __global__ __launch_bounds__(256, 1) void ptail_split_kernel(const SParams p) {
                     lp[g][0] = ul.x;
                     lp[g][1] = ul.y;
                 }
-                typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
                 if (p.out_hi) {
 #pragma unroll
-                    for (int m = 0; m < 2; ++m) {
-                        auto s0 = __builtin_amdgcn_permlane32_swap(hp[2 * m][0], hp[2 * m + 1][0], false, false);
-                        auto s1 = __builtin_amdgcn_permlane32_swap(hp[2 * m][1], hp[2 * m + 1][1], false, false);
-                        const uintx4 raw = {s0[0], s1[0], s0[1], s1[1]};
-                        if (valid)
-                            *(uintx4*)(p.out_hi + (long)img * p.out_hi_img_b + (long)mb * p.out_plane_b + (long)(Y + p.out_border) * p.out_row_b +
-                                       (X + p.out_border) * p.out_pix_b + m * 32 + hi * 16) = raw;
-                    }
+                    for (int m = 0; m < 2; ++m) store16_pair(out_hi, valid, img, mb, Y, X, m, hi, hp[2 * m], hp[2 * m + 1]);
                 }
                 if (p.out_lo) {
 #pragma unroll
-                    for (int m = 0; m < 2; ++m) {
-                        auto s0 = __builtin_amdgcn_permlane32_swap(lp[2 * m][0], lp[2 * m + 1][0], false, false);
-                        auto s1 = __builtin_amdgcn_permlane32_swap(lp[2 * m][1], lp[2 * m + 1][1], false, false);
-                        const uintx4 raw = {s0[0], s1[0], s0[1], s1[1]};
-                        if (valid)
-                            *(uintx4*)(p.out_lo + (long)img * p.out_lo_img_b + (long)mb * p.out_plane_b + (long)(Y + p.out_border) * p.out_row_b +
-                                       (X + p.out_border) * p.out_pix_b + m * 32 + hi * 16) = raw;
-                    }
+                    for (int m = 0; m < 2; ++m) store16_pair(out_lo, valid, img, mb, Y, X, m, hi, lp[2 * m], lp[2 * m + 1]);
                 }
             }
         }
@@ -293,21 +263,12 @@ __global__ __launch_bounds__(256) void split_lo_kernel(const float* __restrict__
 
 template <int UPS>
 int launch(const SParams& p0, hipStream_t stream) {
-    constexpr int LDS_B = W_RES_B + 2 * TileGeo<UPS>::UNITS * 16;
+    constexpr int LDS_B = TAIL_LDS_B<UPS>;
     static_assert(LDS_B <= 163840, "one weight set + one pair of input chunks must fit the 160 KiB LDS");
     SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)ptail_split_kernel<UPS>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B)));
-    static int ncu_of[64] = {0};   // CU count per device (queried once each)
-    int dev = 0;
-    SRBH_HIP(hipGetDevice(&dev));
-    if (!ncu_of[dev & 63]) SRBH_HIP(hipDeviceGetAttribute(&ncu_of[dev & 63], hipDeviceAttributeMultiprocessorCount, dev));
-    int ncu = ncu_of[dev & 63];
-    const int cap = srbh_ptail_wgs_cap(0);      // the caller's cap on the persistent tail's workgroups holds here too (read and put back)
-    srbh_ptail_wgs_cap(cap);
-    if (cap > 0 && cap < ncu) ncu = cap;
     SParams p = p0;
-    const int nwg = p.ntiles < ncu ? p.ntiles : ncu;
-    p.tiles_per_wg = (p.ntiles + nwg - 1) / nwg;
-    const int grid = (p.ntiles + p.tiles_per_wg - 1) / p.tiles_per_wg;
+    int grid = 0;
+    if (const int rc = tail_grid(p.ntiles, &p.tiles_per_wg, &grid)) return rc;      // (the caller's srbh_ptail_wgs_cap holds here too)
     hipLaunchKernelGGL(ptail_split_kernel<UPS>, dim3(grid), dim3(256), LDS_B, stream, p);
     SRBH_HIP(hipGetLastError());
     return SRBH_OK;
@@ -332,15 +293,14 @@ extern "C" int srbh_conv3x3_f16x2(const srbh_conv3x3_args* a, const srbh_conv3x3
                  "srbh_conv3x3_f16x2: an ACT16 output needs its lo' planes (out16_lo)");
     SRBH_REQUIRE(!a->out16_nhwc || (a->out16 && !a->out32), "srbh_conv3x3_f16x2: out16_nhwc excludes an fp32 output");
     const int tiles_x = (a->W + TILE_W - 1) / TILE_W, tiles_y = (a->H + TILE_H - 1) / TILE_H;
-    const int inH = a->upsample2x ? a->H / 2 : a->H, inW = a->upsample2x ? a->W / 2 : a->W;
-    const Act16Geo gh = act16_geo(a->B, a->in_chunks_total, inH, inW), gl = act16_geo(a->B, s->in_lo_chunks_total, inH, inW);
+    const In16 ih = tail_in16(a, a->in, a->in_chunks_total, a->in_chunk0), il = tail_in16(a, s->in_lo, s->in_lo_chunks_total, s->in_lo_chunk0);
     SParams p{};
-    p.in_hi = (const char*)a->in + (long)a->in_chunk0 * gh.plane_b;
-    p.in_lo = (const char*)s->in_lo + (long)s->in_lo_chunk0 * gl.plane_b;
-    p.in_hi_img_b = gh.img_b;
-    p.in_lo_img_b = gl.img_b;
-    p.in_plane_b = gh.plane_b;
-    p.in_row_b = gh.row_b;
+    p.in_hi = ih.base;
+    p.in_lo = il.base;
+    p.in_hi_img_b = ih.img_b;
+    p.in_lo_img_b = il.img_b;
+    p.in_plane_b = ih.plane_b;
+    p.in_row_b = ih.row_b;
     p.w_hi = (const char*)a->w;
     p.w_lo = (const char*)s->w_lo;
     p.bias = a->bias;
@@ -351,24 +311,17 @@ extern "C" int srbh_conv3x3_f16x2(const srbh_conv3x3_args* a, const srbh_conv3x3
     p.tiles_per_img = tiles_x * tiles_y;
     p.ntiles = p.tiles_per_img * a->B;
     p.lrelu = a->lrelu;
-    if (a->out16 && a->out16_nhwc) {
-        const int C = a->out16_chunks_total * 32;
-        p.out_hi = (char*)a->out16 + (long)a->out16_chunk0 * 64;
-        p.out_pix_b = C * 2;
-        p.out_row_b = a->W * C * 2;
-        p.out_hi_img_b = (long)a->H * a->W * C * 2;
-        p.out_plane_b = 64;
-        p.out_border = 0;
-    } else if (a->out16) {
-        const Act16Geo go = act16_geo(a->B, a->out16_chunks_total, a->H, a->W), gol = act16_geo(a->B, s->out16_lo_chunks_total, a->H, a->W);
-        p.out_pix_b = PIX_B;
-        p.out_border = 1;
-        p.out_hi = (char*)a->out16 + (long)a->out16_chunk0 * go.plane_b;
-        p.out_lo = (char*)s->out16_lo + (long)s->out16_lo_chunk0 * gol.plane_b;
-        p.out_hi_img_b = go.img_b;
-        p.out_lo_img_b = gol.img_b;
-        p.out_plane_b = go.plane_b;
-        p.out_row_b = go.row_b;
+    const Out16 oh = tail_out16(a, a->out16, a->out16_chunks_total, a->out16_chunk0);
+    p.out_hi = oh.base;
+    p.out_hi_img_b = oh.img_b;
+    p.out_plane_b = oh.plane_b;
+    p.out_row_b = oh.row_b;
+    p.out_pix_b = oh.pix_b;
+    p.out_border = oh.border;
+    if (a->out16 && !a->out16_nhwc) {
+        const Out16 ol = tail_out16(a, s->out16_lo, s->out16_lo_chunks_total, s->out16_lo_chunk0);
+        p.out_lo = ol.base;
+        p.out_lo_img_b = ol.img_b;
     }
     p.out32 = a->out32;
     return a->upsample2x ? launch<1>(p, stream) : launch<0>(p, stream);

@@ -173,3 +173,57 @@ def test_split_lo_kernel_and_lo_pack_are_the_contract():
     for chunk, tap, ks, mb, lane, j in [(0, 0, 0, 0, 0, 0), (1, 4, 1, 1, 37, 5), (0, 8, 1, 0, 63, 7)]:
         oc, ic = mb * 32 + (lane & 31), chunk * 32 + ks * 16 + (lane >> 5) * 8 + j
         assert raw[chunk, tap, ks, mb, lane, j] == w_lo[oc, ic, tap // 3, tap % 3]
+
+
+# (B, output H, W, nearest-x2 read + LeakyReLU, workgroup cap): a ragged single image with the plain and the nearest-x2 read; 12 full tiles walked
+# by two workgroups, six each, so the resident weights and the next-tile prefetch of both kernels run
+SHARED_PASS = {"ragged-1": (1, 20, 72, False, 0), "ragged-1-ups": (1, 20, 72, True, 0), "walk-6": (3, 16, 128, False, 2)}
+
+
+@pytest.mark.parametrize("geo", list(SHARED_PASS))
+def test_zero_low_parts_give_the_fp16_kernels_bits(geo):
+    """lo' planes and the w_lo pack all zero, no skip: passes 0 and 1 leave every accumulator at +0, the 2^-11 rescale keeps it there and pass 2
+    is the fp16 kernel's own accumulation (the same 288-MFMA pass in the same order) -- so srbh_conv3x3_f16x2 equals srbh_conv3x3_f16
+    on the same hi planes, w_hi pack and bias bit for bit: the fp16 NHWC hand-off (which sends srbh_conv3x3_f16 to ptail_kernel at any size), the
+    ACT16 hi planes and the fp32 NHWC output (against whichever form srbh_conv3x3_f16 selects; tests/test_gpu_conv.py ties the forms together)."""
+    B, H, W, ups, cap = SHARED_PASS[geo]
+    L = _lib.lib()
+    g = torch.Generator().manual_seed(77)
+    ih, iw = (H // 2, W // 2) if ups else (H, W)
+    v = torch.randn(B, ih, iw, 64, generator=g).to(DEV)
+    w = (torch.randn(64, 64, 3, 3, generator=g) * 0.05).to(DEV)
+    bias = (torch.randn(64, generator=g) * 0.05).to(DEV)
+    inbuf = G.act16_alloc(B, 4, ih, iw, DEV)                       # hi in planes 0..1; planes 2..3 (lo') stay zero
+    _lib.check(L.srbh_nhwc32_to_act16(v.data_ptr(), inbuf.data_ptr(), B, 64, ih, iw, 4, 0, 1.0, 0, _lib.stream_ptr()), "nhwc32_to_act16")
+    wh = G.pack_w(w)
+    wl = torch.zeros_like(wh)
+
+    def args(**out):
+        return G.conv_args(**{"in": inbuf.data_ptr()}, in_chunks_total=4, in_chunk0=0, in_chunks=2, w=wh.data_ptr(), bias=bias.data_ptr(), cout=64,
+                           B=B, H=H, W=W, upsample2x=int(ups), lrelu=int(ups), **out)
+
+    def run(split):
+        p16 = G.act16_alloc(B, 4 if split else 2, H, W, DEV)
+        o32 = torch.full((B, H, W, 64), float("nan"), dtype=torch.float32, device=DEV)
+        n16 = torch.full((B, H, W, 64), float("nan"), dtype=torch.float16, device=DEV)
+        for a in (args(out16=p16.data_ptr(), out16_chunks_total=4 if split else 2, out16_chunk0=0, out32=o32.data_ptr(), out32_c=64),
+                  args(out16=n16.data_ptr(), out16_chunks_total=2, out16_chunk0=0, out16_nhwc=1)):
+            if split:
+                s = _lib.ConvSplit(in_lo=inbuf.data_ptr(), in_lo_chunks_total=4, in_lo_chunk0=2, w_lo=wl.data_ptr(),
+                                   out16_lo=p16.data_ptr(), out16_lo_chunks_total=4, out16_lo_chunk0=2)
+                _lib.check(L.srbh_conv3x3_f16x2(C.byref(a), C.byref(s), _lib.stream_ptr()), "conv3x3_f16x2")
+            else:
+                G.run_conv(a)
+        torch.cuda.synchronize()
+        assert not bool(torch.isnan(o32).any() or torch.isnan(n16).any()) and G.border_is_zero(p16, B, 4 if split else 2, H, W)
+        hi = G.act16_planes(p16, B, 4 if split else 2, H, W, torch.int16)[:, :64]
+        return n16.view(torch.int16), hi, o32.view(torch.int32)
+
+    prev = L.srbh_ptail_wgs_cap(cap)
+    try:
+        got, want = run(True), run(False)
+    finally:
+        L.srbh_ptail_wgs_cap(prev)
+    for what, a, b in zip(("fp16 NHWC hand-off", "ACT16 hi planes", "fp32 NHWC"), got, want):
+        assert bool(b.any()), what
+        assert torch.equal(a, b), f"{what}: {int((a != b).sum())} of {a.numel()} elements differ"

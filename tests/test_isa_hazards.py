@@ -11,7 +11,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 @pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="no hipcc")
-@pytest.mark.parametrize("src", ["srbh_ptrunk.hip", "srbh_ptail.hip", "srbh_conv3x3.hip"])
+@pytest.mark.parametrize("src", ["srbh_ptrunk.hip", "srbh_ptail.hip", "srbh_ptail_split.hip", "srbh_conv3x3.hip"])
 def test_no_unseen_hazards_around_inline_asm(src, tmp_path):
     out = str(tmp_path / (src + ".s"))
     cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-inline-asm", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
