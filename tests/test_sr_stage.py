@@ -457,6 +457,60 @@ def test_persistent_training_backward_follows_the_per_layer_sequence(blocks, B):
 
 
 @pytest.mark.gpu
+def test_per_layer_training_backward_on_one_stream_equals_the_side_stream_order():
+    """srbh_rrdbnet_trunk_train_backward (the gradient of SR/rrdbnet_arch.py:136-167 per RDB, layer by layer) issues the same launches in two
+    orders: with two G buffers (g_stride > 0, what the Python path passes) an RDB's weight / bias gradients start on a side stream and its dx conv
+    is issued behind them; with g_stride = 0 (one G buffer, no side stream) dx comes first and everything runs on the caller's stream.  Same
+    launches on the same saved planes and the same output gradient: the input gradient and dw_all are bit-identical.  db_all is not, in either
+    order and from run to run: srbh_act16_channel_sum adds its per-wave partial sums with fp32 atomics, so their order is the hardware's (seen
+    with the two orders still written out separately: db_all differs between two runs of one build and one setting by 6.6e-8 .. 8.6e-8 rel-L2, and
+    between the two orders here by 8.5e-8).  It is held to the bound of test_persistent_training_backward_follows_the_per_layer_sequence, 2e-3
+    rel-L2."""
+    import ctypes as C
+    from srbh_amd import _lib
+    from srbh_amd import rrdbnet_autograd as RA
+    from srbh_amd import synth
+    from srbh_amd.rrdbnet import RRDBNet
+    blocks, B = 1, 2
+    n_rdb = blocks * 3
+    net = RRDBNet(3, 3, num_block=blocks)
+    net.load_state_dict(synth.rrdbnet_state_dict(num_block=blocks, seed=5, mode="stress"))
+    net = net.to("cuda:0")
+    feat = rand((B, 64, 64, 64), 31).to("cuda:0").contiguous()
+    g = rand((B, 64, 64, 64), 32, -1.0, 1.0).to("cuda:0").contiguous()
+    RA._FAST_WS.clear()
+    xr, lease = RA._trunk_fast_forward(net, feat)
+    res = []
+    try:
+        ws = lease.ws
+        packs = net.__dict__.setdefault("_srbh_trunk_bwd_packs", RA._TrunkBwdPacks()).get(net)
+        offs = (C.c_size_t * 5)(*packs.offs)
+        assert ws["G"].numel() >= 2 * ws["nb"]
+        for g_stride in (ws["nb"], 0):
+            ga, gb, gc = g.clone(), torch.empty_like(g), torch.empty_like(g)
+            dw_all = torch.empty(n_rdb * RA._DW_RDB, dtype=torch.float32, device=g.device)
+            db_all = torch.empty(n_rdb * 192, dtype=torch.float32, device=g.device)
+            gout = C.c_void_p()
+            _lib.check(_lib.lib().srbh_rrdbnet_trunk_train_backward(blocks, ws["D"].data_ptr(), ws["nb"], packs.buf.data_ptr(), packs.stride, offs,
+                                                                    ga.data_ptr(), gb.data_ptr(), gc.data_ptr(), C.byref(gout), ws["G"].data_ptr(), g_stride,
+                                                                    dw_all.data_ptr(), db_all.data_ptr(), ws["wg"].data_ptr(), B, 64, 64, _lib.stream_ptr()),
+                       "rrdbnet_trunk_train_backward")
+            torch.cuda.synchronize()
+            gin = {t.data_ptr(): t for t in (ga, gb, gc)}[gout.value]
+            res.append((gin, dw_all, db_all))
+    finally:
+        lease.release()
+        RA._FAST_WS.clear()
+    for t in res[0]:
+        assert bool(torch.isfinite(t).all()) and float(t.abs().max()) > 0
+    db_err = O.rel_l2(res[0][2].cpu(), res[1][2].cpu())
+    print(f"db_all, side-stream order vs one stream: rel-L2 {db_err:.3e}")
+    assert torch.equal(res[0][0], res[1][0]), "input gradient"
+    assert torch.equal(res[0][1], res[1][1]), "dw_all"
+    assert db_err <= 2e-3, db_err
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("blocks,B,Hh", [(1, 2, 64), (2, 5, 64), (1, 1, 128)])
 def test_one_launch_trunk_weight_gradients_equal_the_general_kernel(blocks, B, Hh):
     """srbh_trunk_wgrad (weight + bias gradients of every RDB's five convs, SR/rrdbnet_arch.py:136-167, as one launch over (RDB, plane pair, tile
