@@ -82,6 +82,38 @@
 #ifndef P3_PRE_AT
 #define P3_PRE_AT 2
 #endif
+#ifndef P3_PAIR
+// 1: a dense-block plane that is still in an LDS input area is not staged again.  With one conv after the other (0) every cout-32 layer
+// re-stages every chunk it reads: per RDB x's second chunk is written into the ring 5 times, X1 4 times, X2 3 times (each 8 ds_write_b128 +
+// a border write + 2 halo DMA statements + a neighbour poll), although conv2's sum over x and conv4's sum over x, X1, X2 need nothing that
+// conv1 / conv3 produce.  The order of an RDB is then ([c: k] = today's 72-MFMA cout-32 step of conv k over chunk c on today's weight piece
+// T[k-1].w + c * 18 KiB; input areas 0 / 1 = the input parts of phase-A stages 0 / 1, which no longer flip with the weight areas):
+//   conv1  [x0:1] (x1 -> area 1)  [x1:1]                                        -> epilogue: X1 (registers + halo rows)
+//   conv2  [x0:2] (x1 -> area 0)  [x1:2] (X1 -> area 1, checks X1)  [X1:2]      -> epilogue: X2 (registers + halo rows)
+//   conv3+4 [x0:3] [x0:4] [x1:3] [x1:4] [X1:3] (X2 -> area 0, checks X2) [X2:3]  -> epilogue conv3: X3 (conv4's accumulator parked)
+//           [X1:4] [X2:4] (X3 -> area 1 by DMA, checks X3) [X3:4] (conv5's first 36 KiB of weights)   -> epilogue conv4: X4
+//   conv5  as before (it re-stages x1, X1, X2 from registers and X3, X4 by DMA into phase-B stages).
+// Register-plane stagings per RDB: 7 instead of 12 (x1: 3, X1: 2, X2: 2); six of the fourteen cout-32 steps stage weights only.  Every
+// accumulator still receives its chunks in the order x0, x1, X1, ..., the (ks, dx, dy) order inside a step and the epilogues are unchanged:
+// same bits.  What decides the order:
+//   * conv1's step-0 weights are prefetched at the seam into area 0 (P3_SEAM), so conv1 stages x1 into area 1; conv4's last step puts
+//     conv5's first weights over area 0, so X3 must sit in area 1, X2 in area 0, X1 in area 1 and x1 in area 0: conv2 (whose steps are
+//     exactly those of the unpaired order) stages x1 once more, into area 0, and from there on nothing is staged twice.  The weight
+//     areas keep alternating per step, so conv2's two staging steps write their input and their weights into DIFFERENT stages
+//     (run_step's `dwo`); everywhere else the two destinations are one stage as before.
+//   * publication before wait: a layer's output is published behind the first step barrier after its epilogue (P3_LAZYDRAIN), and only a
+//     LATER step may check the neighbours for it.  conv4's [X1:4] and [X2:4] are therefore held back behind conv3's epilogue (X1 and X2
+//     are both still staged, so this costs no staging): X3's stores drain under [X1:4], its barrier publishes X3, and [X2:4] polls at its
+//     top and fetches X3 under its MFMAs exactly as conv4's step 3 did.  (Pairing [X1:4] in front of the epilogue as well would put X3's
+//     check into the step whose barrier publishes X3: two neighbours would wait for each other.)  conv1 + conv2 need no pairing at all:
+//     x1 is simply still there.
+//   * the layer indices of every step are compile-time (one body per position): an accumulator parked across an epilogue under a
+//     run-time layer index once cost 217 spilled registers; here all four forms stay at 0 bytes of scratch (tests/test_isa_registers.py).
+// SRBH_PT_PROF keeps six slots per layer.  conv3's slots cover the shared pass (its K-loop time and barrier waits include conv4's three
+// interleaved steps), conv4's cover what is left of it: the prologue behind conv3's epilogue, its last three steps and its epilogue.
+// 0 compiles the unpaired order (tools/build_variant.py, tools/ab_variants.sh).
+#define P3_PAIR 1
+#endif
 
 // PROF = 1 (developer timeline, SRBH_PT_PROF): s_memtime stamps per layer in ptrunk_kernel's 6-slot format
 // BW = 1 (round 5): the BACKWARD of the dense blocks on the same instruction stream.  The data gradient of an RDB is an RDB run on
@@ -336,9 +368,12 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
     // ---- one K step.  CB = cout/32 of the running layer.  What is staged for the NEXT step is a compile-time property:
     //   IN: 0 no input plane | 1 input plane by LDS-DMA (11 statements) | 2 input plane from registers (8 ds_write_b128 + 1
     //   border write + 2 halo DMA statements);   NW: weight DMA statements per wave (0 | 5 = 18 fragments | 9 = 36 fragments)
+    // The step reads its input plane at sbi and its weights at sbw; it stages the next input chunk at dst and the next weights at dst + dwo
+    // (IN_EX: one stage, as everywhere but in conv2 under P3_PAIR); nbi is the input plane the NEXT step reads (pre-read of its group 0):
+    // dst where this step staged it, else a plane that is already there (the resident plane, or an input area an earlier step filled).
     auto run_step = [&](auto cb_tag, auto in_tag, auto nw_tag, floatx16 (&acc)[decltype(cb_tag)::value][4], const char* sbi, const char* sbw,
                         const char* nsrc, const char* nw, char* dst, const uintx4 (&rsrc)[4][2], auto flag_tag, const int need,
-                        auto pre_tag, auto nxt_tag) {
+                        auto pre_tag, auto nxt_tag, const int dwo, const char* nbi) {
         constexpr int CB = decltype(cb_tag)::value, IN = decltype(in_tag)::value, NW = decltype(nw_tag)::value;
         // FL: this step fetches rows of a neighbour (the plane it stages is new on them): polls at the top, the check in front of the
         // statements that carry those rows, which are then the LAST staging items of the step (need < 0: no check this time)
@@ -358,7 +393,7 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
         const unsigned long long ibase = uni64((unsigned long long)nsrc);
         const unsigned long long wbase = uni64((unsigned long long)(nw + wave * 1024));
         const unsigned din_w = __builtin_amdgcn_readfirstlane(lds_addr(dst) + wave * 1024);
-        const unsigned dw_w = din_w + IN_EX;
+        const unsigned dw_w = din_w + dwo;
         constexpr bool PRE = decltype(pre_tag)::value != 0;    // group 0's operands were read by the previous step
         constexpr bool NXT = decltype(nxt_tag)::value != 0;    // this step holds the barrier and reads the next step's group 0 (same layer)
         constexpr int AT = P3_PRE_AT < NMF - NRD ? P3_PRE_AT : NMF - NRD;   // MFMA of the last group the barrier sits in front of
@@ -454,9 +489,9 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
                 __builtin_amdgcn_sched_barrier(0);
                 const int k = m / RSTRIDE;
                 if (g + 1 < 6 && m % RSTRIDE == 0 && k < NRD) read_item(g + 1, CB == 1 ? ORD1[k % 9] : ORD2[k % 12], (g + 1) & 1);
-                if constexpr (NXT) {                 // the next step's group 0 (it reads what this step staged: dst, dst + IN_EX), one read per shadow
+                if constexpr (NXT) {                 // the next step's group 0 (its input plane: nbi; its weights: what this step staged at dst + dwo), one read per shadow
                     const int k2 = m - AT;
-                    if (g == 5 && k2 >= 0 && k2 < NRD) read_from(dst, dst + IN_EX, 0, CB == 1 ? ORD1[k2 % 9] : ORD2[k2 % 12], 0);
+                    if (g == 5 && k2 >= 0 && k2 < NRD) read_from(nbi, dst + dwo, 0, CB == 1 ? ORD1[k2 % 9] : ORD2[k2 % 12], 0);
                 }
                 // staging: one item per shadow for a cout-32 group (12), every other shadow of conv5's (the ones without a read)
                 const int sm = CB == 1 ? m : (m % 2 ? m / 2 : -1);
@@ -738,6 +773,7 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
     //  conv5's last step can prefetch them at the seam)
     stage_cold(dcur, smem, pp.layers[0].w, smem + stage_off(1, 0) + (P3_SEAM ? 0 : IN_EX), W5{});
     const int nrdb = pp.nlayers / 5;
+    constexpr bool PAIR = P3_PAIR != 0;
     for (int rdb = 0; rdb < nrdb; ++rdb) {
         const PLayer* T = pp.layers + rdb * 5;
         const int L0 = rdb * 5;
@@ -748,6 +784,7 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
         float next_bias = 0.f;   // the next layer's bias element of this thread, requested ahead of the epilogue
         auto layerA = [&](auto kk_tag, auto last_nw_tag) {
             constexpr int kk = decltype(kk_tag)::value;
+            constexpr bool XS = PAIR && kk == 1;
             const int L = L0 + kk, n = kk + 2;
             const char* wl = T[kk].w;
             unsigned long long p0 = 0, p1 = 0, p2 = 0;
@@ -770,36 +807,55 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
             // step 0: resident plane 0; stages chunk 1 (x's second half) from registers.  Its barrier (inside its last MFMA group) is the
             // layer's FIRST: it carries the lazy publication of the previous layer's output (its vmcnt(0) covers the epilogue stores that
             // drained under step 0), in front of any neighbour check of this layer
-            run_step(C1{}, I2{}, W5{}, acc, smem, smem + stage_off(1, gs & 1) + ((P3_SEAM && kk == 0) ? 0 : IN_EX), dcur + (long)pp.plane_b, wl + 18 * 1024,
-                     smem + stage_off(1, (gs + 1) & 1), x1p, F0{}, 0, Q0{}, Q1{});
+            // (XS, conv2 under P3_PAIR: x's second chunk goes to input area 0 and X1 to area 1, where the conv3 + conv4 pass finds them;
+            //  the weight areas keep alternating per step, so these two steps stage their input and their weights into different stages)
+            if constexpr (XS) {
+                run_step(C1{}, I2{}, W5{}, acc, smem, smem + stage_off(1, 0) + IN_EX, dcur + (long)pp.plane_b, wl + 18 * 1024,
+                         smem + stage_off(1, 0), x1p, F0{}, 0, Q0{}, Q1{}, IN_EX + A_STAGE_B, smem + stage_off(1, 0));
+            } else {
+                char* dst = smem + stage_off(1, (gs + 1) & 1);
+                run_step(C1{}, I2{}, W5{}, acc, smem, smem + stage_off(1, gs & 1) + ((P3_SEAM && kk == 0) ? 0 : IN_EX), dcur + (long)pp.plane_b, wl + 18 * 1024,
+                         dst, x1p, F0{}, 0, Q0{}, Q1{}, IN_EX, dst);
+            }
             ++gs;
             // The only NEW input plane of conv2..4 is the last chunk (index kk + 1): its halo rows are fetched during step kk, which checks
             // the neighbours' progress itself (conv1's inputs were verified at the seam).
             if (n >= 3) {      // step 1: chunk 1; stages chunk 2 (X1) from registers
-                const char* st = smem + stage_off(1, gs & 1);
-                run_step(C1{}, I2{}, W5{}, acc, st, st + IN_EX, dcur + 2l * pp.plane_b, wl + 2 * (18 * 1024),
-                         smem + stage_off(1, (gs + 1) & 1), X1r, std::integral_constant<int, kk == 1>{}, L, Q1{}, Q1{});
+                if constexpr (XS) {
+                    run_step(C1{}, I2{}, W5{}, acc, smem + stage_off(1, 0), smem + stage_off(1, 1) + IN_EX, dcur + 2l * pp.plane_b, wl + 2 * (18 * 1024),
+                             smem + stage_off(1, 1), X1r, F1{}, L, Q1{}, Q1{}, IN_EX - A_STAGE_B, smem + stage_off(1, 1));
+                } else {
+                    const char* st = smem + stage_off(1, gs & 1);
+                    char* dst = smem + stage_off(1, (gs + 1) & 1);
+                    run_step(C1{}, I2{}, W5{}, acc, st, st + IN_EX, dcur + 2l * pp.plane_b, wl + 2 * (18 * 1024),
+                             dst, X1r, std::integral_constant<int, kk == 1>{}, L, Q1{}, Q1{}, IN_EX, dst);
+                }
                 ++gs;
             }
             if (n >= 4) {      // step 2: chunk 2; stages chunk 3 (X2) from registers
                 const char* st = smem + stage_off(1, gs & 1);
+                char* dst = smem + stage_off(1, (gs + 1) & 1);
                 run_step(C1{}, I2X{}, W5{}, acc, st, st + IN_EX, dcur + 3l * pp.plane_b, wl + 3 * (18 * 1024),
-                         smem + stage_off(1, (gs + 1) & 1), X2r, std::integral_constant<int, kk == 2>{}, L, Q1{}, Q1{});
+                         dst, X2r, std::integral_constant<int, kk == 2>{}, L, Q1{}, Q1{}, IN_EX, dst);
                 ++gs;
             }
             if (n >= 5) {      // step 3 (conv4): chunk 3; stages chunk 4 (X3) by DMA
                 const char* st = smem + stage_off(1, gs & 1);
+                char* dst = smem + stage_off(1, (gs + 1) & 1);
                 run_step(C1{}, I1{}, W5{}, acc, st, st + IN_EX, dcur + 4l * pp.plane_b, wl + 4 * (18 * 1024),
-                         smem + stage_off(1, (gs + 1) & 1), x1p, F1{}, L, Q1{}, Q1{});
+                         dst, x1p, F1{}, L, Q1{}, Q1{}, IN_EX, dst);
                 ++gs;
             }
             {
                 const char* st = smem + stage_off(1, gs & 1);
                 // (the last step reads chunk kk + 1: x's second half, X1, X2 -- register-resident -- or X3)
-                if constexpr (decltype(last_nw_tag)::value == 5)   // conv1..3: the next layer's step 0 reads the resident plane: weights only
-                    run_step(C1{}, I0{}, W5{}, acc, st, st + IN_EX, nullptr, T[kk + 1].w, smem + stage_off(1, (gs + 1) & 1), x1p, F0{}, 0, Q1{}, Q0{});
+                if constexpr (XS)   // (conv2 under P3_PAIR: X1 sits in input area 1, this step's weights in stage 0)
+                    run_step(C1{}, I0{}, W5{}, acc, smem + stage_off(1, 1), smem + stage_off(1, 0) + IN_EX, nullptr, T[kk + 1].w, smem + stage_off(1, 1), x1p, F0{}, 0, Q1{},
+                             Q0{}, IN_EX, smem);
+                else if constexpr (decltype(last_nw_tag)::value == 5)   // conv1..3: the next layer's step 0 reads the resident plane: weights only
+                    run_step(C1{}, I0{}, W5{}, acc, st, st + IN_EX, nullptr, T[kk + 1].w, smem + stage_off(1, (gs + 1) & 1), x1p, F0{}, 0, Q1{}, Q0{}, IN_EX, smem);
                 else              // conv4: conv5's chunk 0 IS the resident plane (phase-B stage 0 starts at the same address): 36 KiB of weights
-                    run_step(C1{}, I0{}, W9{}, acc, st, st + IN_EX, nullptr, T[4].w, smem + stage_off(2, 0), x1p, F0{}, 0, Q1{}, Q0{});
+                    run_step(C1{}, I0{}, W9{}, acc, st, st + IN_EX, nullptr, T[4].w, smem + stage_off(2, 0), x1p, F0{}, 0, Q1{}, Q0{}, IN_EX, smem);
                 ++gs;
             }
             if (P3_LAZYDRAIN) next_bias = bias_request(T[kk + 1].bias, kk == 3 ? 64 : 32);   // (older than the epilogue's stores)
@@ -829,8 +885,79 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
         };
         layerA(std::integral_constant<int, 0>{}, W5{});
         layerA(std::integral_constant<int, 1>{}, W5{});
-        layerA(std::integral_constant<int, 2>{}, W5{});
-        layerA(std::integral_constant<int, 3>{}, W9{});
+        if constexpr (!PAIR) {
+            layerA(std::integral_constant<int, 2>{}, W5{});
+            layerA(std::integral_constant<int, 3>{}, W9{});
+        } else {
+            // ---------------- conv3 + conv4 in ONE pass over the planes they share (P3_PAIR; the order and its reasons: header).  Nine step
+            // bodies, each today's cout-32 step on today's weight piece T[k].w + chunk * 18 KiB; two accumulators live (conv5's 128 registers).
+            // On entry conv2 has left x's second chunk in input area 0 and X1 in area 1, and this pass's first weights in stage 1.
+            const int L3 = L0 + 2, L4 = L0 + 3;
+            const char* w3 = T[2].w;
+            const char* w4 = T[3].w;
+            constexpr int WP = 18 * 1024;
+            char* const s0 = smem + stage_off(1, 0);   // stage k: input area k, weight area k behind it
+            char* const s1 = smem + stage_off(1, 1);
+            unsigned long long p0 = 0, p1 = 0, p2 = 0;
+            if (PROF) p0 = __builtin_amdgcn_s_memtime();
+            if (P3_LAZYDRAIN) {
+                constexpr bool prev_halo_only = P3_SKIPST && P3_S1 && P3_X2REG;    // X2's stores in flight: one halo row, or the whole plane
+                prologue(std::integral_constant<int, prev_halo_only ? 2 : 8>{}, next_bias, 32, A_BIAS_OFF);
+            } else {
+                prologue_cold(T[2].bias, 32, A_BIAS_OFF);
+            }
+            if (PROF) p1 = __builtin_amdgcn_s_memtime();
+            t_sync = 0;
+            t_vm = 0;
+            floatx16 acc3[1][4], acc4[1][4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc3[0][i][r] = acc4[0][i][r] = 0.f;
+            // x0 (resident): conv3, conv4.  The first barrier carries the lazy publication of X2.
+            run_step(C1{}, I0{}, W5{}, acc3, smem, s1 + IN_EX, nullptr, w4, s0, x1p, F0{}, 0, Q0{}, Q1{}, IN_EX, smem);
+            run_step(C1{}, I0{}, W5{}, acc4, smem, s0 + IN_EX, nullptr, w3 + WP, s1, x1p, F0{}, 0, Q1{}, Q1{}, IN_EX, s0);
+            // x's second chunk (area 0, staged by conv2): conv3, conv4
+            run_step(C1{}, I0{}, W5{}, acc3, s0, s1 + IN_EX, nullptr, w4 + WP, s0, x1p, F0{}, 0, Q1{}, Q1{}, IN_EX, s0);
+            run_step(C1{}, I0{}, W5{}, acc4, s0, s0 + IN_EX, nullptr, w3 + 2 * WP, s1, x1p, F0{}, 0, Q1{}, Q1{}, IN_EX, s1);
+            // X1 (area 1, staged by conv2): conv3 -- stages X2 from registers into area 0 and checks the neighbours for it -- then X2: conv3
+            run_step(C1{}, I2X{}, W5{}, acc3, s1, s1 + IN_EX, dcur + 3l * pp.plane_b, w3 + 3 * WP, s0, X2r, F1{}, L3, Q1{}, Q1{}, IN_EX, s0);
+            run_step(C1{}, I0{}, W5{}, acc3, s0, s0 + IN_EX, nullptr, w4 + 2 * WP, s1, x1p, F0{}, 0, Q1{}, Q0{}, IN_EX, smem);
+            if (P3_LAZYDRAIN) next_bias = bias_request(T[3].bias, 32);
+            if (PROF) p2 = __builtin_amdgcn_s_memtime();
+            uintx4 kept[4][2];
+            epi32(acc3, dcur + 4l * pp.plane_b - (long)Y0 * pp.row_b, kept, false, BW ? mcur + 3l * pp.plane_b - (long)Y0 * pp.row_b : nullptr);
+            pending_pub = true;
+            pub_val = L3 + 1;
+            if (PROF && tid == 0) {
+                unsigned long long* q = pp.prof + ((long)blockIdx.x * pp.nlayers + L3) * 6;
+                q[0] = p1; q[1] = p2; q[2] = __builtin_amdgcn_s_memtime(); q[3] = p1 - p0; q[4] = t_sync; q[5] = t_vm;
+            }
+            // conv4's accumulator was parked across that epilogue; its X1 and X2 steps run while X3's stores drain, the first barrier publishes
+            // X3, and the X2 step -- in front of which every neighbour has therefore had a whole step to publish -- fetches X3 (area 1)
+            if (PROF) p0 = __builtin_amdgcn_s_memtime();
+            if (P3_LAZYDRAIN) {
+                prologue(std::integral_constant<int, 8>{}, next_bias, 32, A_BIAS_OFF);
+            } else {
+                prologue_cold(T[3].bias, 32, A_BIAS_OFF);
+            }
+            if (PROF) p1 = __builtin_amdgcn_s_memtime();
+            t_sync = 0;
+            t_vm = 0;
+            run_step(C1{}, I0{}, W5{}, acc4, s1, s1 + IN_EX, nullptr, w4 + 3 * WP, s0, x1p, F0{}, 0, Q0{}, Q1{}, IN_EX, s0);
+            run_step(C1{}, I1{}, W5{}, acc4, s0, s0 + IN_EX, dcur + 4l * pp.plane_b, w4 + 4 * WP, s1, x1p, F1{}, L4, Q1{}, Q1{}, IN_EX, s1);
+            // X3; conv5's chunk 0 IS the resident plane (phase-B stage 0 starts at the same address): 36 KiB of weights behind it
+            run_step(C1{}, I0{}, W9{}, acc4, s1, s1 + IN_EX, nullptr, T[4].w, smem + stage_off(2, 0), x1p, F0{}, 0, Q1{}, Q0{}, IN_EX, smem);
+            if (P3_LAZYDRAIN) next_bias = bias_request(T[4].bias, 64);
+            if (PROF) p2 = __builtin_amdgcn_s_memtime();
+            epi32(acc4, dcur + 5l * pp.plane_b - (long)Y0 * pp.row_b, kept, false, BW ? mcur + 2l * pp.plane_b - (long)Y0 * pp.row_b : nullptr);
+            pending_pub = true;
+            pub_val = L4 + 1;
+            if (PROF && tid == 0) {
+                unsigned long long* q = pp.prof + ((long)blockIdx.x * pp.nlayers + L4) * 6;
+                q[0] = p1; q[1] = p2; q[2] = __builtin_amdgcn_s_memtime(); q[3] = p1 - p0; q[4] = t_sync; q[5] = t_vm;
+            }
+        }
         // ---------------- conv5 (cout 64, stages of IN_EX + 36 KiB, residual epilogue)
         {
             const int L = L0 + 4;
@@ -854,23 +981,24 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
                     for (int r = 0; r < 16; ++r) acc[mb][i][r] = 0.f;
             {   // chunk 0 = the resident plane (in place: phase-B stage 0); stages chunk 1 from registers
                 const char* st = smem + stage_off(2, 0);
-                run_step(C2{}, I2{}, W9{}, acc, st, st + IN_EX, dcur + (long)pp.plane_b, wl + 36 * 1024, smem + stage_off(2, 1), x1p, F0{}, 0, Q0{}, Q1{});
+                run_step(C2{}, I2{}, W9{}, acc, st, st + IN_EX, dcur + (long)pp.plane_b, wl + 36 * 1024, smem + stage_off(2, 1), x1p, F0{}, 0, Q0{}, Q1{}, IN_EX, smem + stage_off(2, 1));
             }
             {   // chunk 1; stages chunk 2 (X1) from registers
                 const char* st = smem + stage_off(2, 1);
-                run_step(C2{}, I2{}, W9{}, acc, st, st + IN_EX, dcur + 2l * pp.plane_b, wl + 2 * (36 * 1024), smem + stage_off(2, 0), X1r, F0{}, 0, Q1{}, Q1{});
+                run_step(C2{}, I2{}, W9{}, acc, st, st + IN_EX, dcur + 2l * pp.plane_b, wl + 2 * (36 * 1024), smem + stage_off(2, 0), X1r, F0{}, 0, Q1{}, Q1{}, IN_EX, smem + stage_off(2, 0));
             }
             {   // chunk 2; stages chunk 3 (X2) from registers
                 const char* st = smem + stage_off(2, 0);
-                run_step(C2{}, I2X{}, W9{}, acc, st, st + IN_EX, dcur + 3l * pp.plane_b, wl + 3 * (36 * 1024), smem + stage_off(2, 1), X2r, F0{}, 0, Q1{}, Q1{});
+                run_step(C2{}, I2X{}, W9{}, acc, st, st + IN_EX, dcur + 3l * pp.plane_b, wl + 3 * (36 * 1024), smem + stage_off(2, 1), X2r, F0{}, 0, Q1{}, Q1{}, IN_EX, smem + stage_off(2, 1));
             }
             {   // chunks 3, 4; stage X3, X4 by DMA (X4 is conv4's output on the neighbours: checked by the step that fetches it).  ONE step body run
                 // twice, as a do-while: the `for` form and two explicit bodies both cost 30 spilled VGPRs (and the two bodies 144 more MFMAs of code)
                 int c = 3;
                 do {
                     const char* st = smem + stage_off(2, c & 1);
+                    char* dst = smem + stage_off(2, (c + 1) & 1);
                     run_step(C2{}, I1{}, W9{}, acc, st, st + IN_EX, dcur + (long)(c + 1) * pp.plane_b, wl + (long)(c + 1) * (36 * 1024),
-                             smem + stage_off(2, (c + 1) & 1), x1p, F1{}, c == 4 ? L : -1, Q1{}, Q1{});
+                             dst, x1p, F1{}, c == 4 ? L : -1, Q1{}, Q1{}, IN_EX, dst);
                 } while (++c < 5);
             }
             {
@@ -879,9 +1007,9 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
                     // the next conv1's first weight chunk -> smem + IN_EX (dst = smem: run_step puts weights at dst + IN_EX); the last RDB has no
                     // successor: it prefetches its own first chunk again (a select, not a branch: one step body), nobody reads it
                     const char* nw5 = rdb + 1 < nrdb ? T[5].w : T[0].w;
-                    run_step(C2{}, I0{}, W5{}, acc, st, st + IN_EX, nullptr, nw5, smem, x1p, F0{}, 0, Q1{}, Q0{});
+                    run_step(C2{}, I0{}, W5{}, acc, st, st + IN_EX, nullptr, nw5, smem, x1p, F0{}, 0, Q1{}, Q0{}, IN_EX, smem);
                 } else {
-                    run_step(C2{}, I0{}, W0{}, acc, st, st + IN_EX, nullptr, nullptr, smem, x1p, F0{}, 0, Q1{}, Q0{});
+                    run_step(C2{}, I0{}, W0{}, acc, st, st + IN_EX, nullptr, nullptr, smem, x1p, F0{}, 0, Q1{}, Q0{}, IN_EX, smem);
                 }
             }
             const bool r2 = (rdb % 3) == 2;
