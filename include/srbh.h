@@ -55,6 +55,12 @@ const char* srbh_last_error(void);
 #define SRBH_PATH_HBLOCK16 11            /* srbh_hblock16_eval: a plain BasicBlock of the inference head in one pass */
 #define SRBH_PATH_HBWD16 10              /* srbh_hbwd16: BatchNorm apply + weight gradient + data gradient of a 16 -> 16 conv in one pass */
 int srbh_path_counters(unsigned long long* out, int n, int reset);
+/* Read-only: the workgroup cap in effect for the persistent tile walk of the kernel behind `path` (SRBH_PATH_HCONV16, _ENTRY_FUSED, _WGRAD16,
+ * _HCONV_UP, _HBWD16, _HBLOCK16; the SRBH_*_WGS environment knobs, read once per process).  A walk over ntiles = B * (H/4) * (W/64) tiles
+ * gives each of the 8 XCDs a contiguous run of tiles_per_xcd = ceil(ntiles / 8) and launches min(tiles_per_xcd, cap / 8) workgroups per XCD;
+ * workgroup j of an XCD takes tiles j, j + that count, ... of its run.  SRBH_PATH_ENTRY_FUSED reports the chunked entry kernel's cap; the
+ * whole-row form of the 64-channel fp16 source always runs 32 workgroups per XCD.  Returns -1 for a path without such a walk. */
+int srbh_head_wgs_cap(int path);
 
 /* ---- layout helpers (used by tests and by the Python mirror at module boundaries) ------------ */
 /* bytes of an ACT16 buffer including the read slack the tiled kernels need */

@@ -66,6 +66,14 @@ def path_counters(reset=False):
     return {k: int(v) for k, v in zip(PATH_NAMES, buf)}
 
 
+def head_wgs_cap(form):
+    """the workgroup cap in effect for the persistent tile walk of a head kernel (`form`: a PATH_NAMES entry; include/srbh.h srbh_head_wgs_cap)"""
+    cap = lib().srbh_head_wgs_cap(PATH_NAMES.index(form))
+    if cap < 0:
+        raise ValueError(f"{form}: no persistent tile walk behind this form")
+    return int(cap)
+
+
 # ---- C structs (mirror include/srbh.h) ------------------------------------------------------------
 class ConvArgs(C.Structure):
     _fields_ = [
@@ -186,6 +194,7 @@ SIGNATURES = {
     "srbh_version": (_i, []),
     "srbh_last_error": (C.c_char_p, []),
     "srbh_path_counters": (_i, [_vp, _i, _i]),
+    "srbh_head_wgs_cap": (_i, [_i]),
     "srbh_act16_bytes": (_sz, [_i, _i, _i, _i]),
     "srbh_nchw32_to_act16": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "srbh_act16_to_nchw32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),

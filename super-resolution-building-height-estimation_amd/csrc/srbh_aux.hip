@@ -46,6 +46,18 @@ extern "C" int srbh_path_counters(unsigned long long* out, int n, int reset) {
     if (reset) for (int i = 0; i < srbh::PATH_N; ++i) srbh::g_path_counters[i] = 0;
     return srbh::PATH_N;
 }
+/* the workgroup cap in effect for the persistent tile walk behind a path id (srbh.h); -1: that form has no such walk */
+extern "C" int srbh_head_wgs_cap(int path) {
+    switch (path) {
+        case PATH_HCONV16: return hconv16_wgs_cap();
+        case PATH_ENTRY_FUSED: return hconv_entry_wgs_cap();
+        case PATH_WGRAD16: return hwgrad16_wgs_cap();
+        case PATH_HCONV_UP: return hconv_up_wgs_cap();
+        case PATH_HBWD16: return hbwd16_wgs_cap();
+        case PATH_HBLOCK16: return hblock16_wgs_cap();
+        default: return -1;
+    }
+}
 extern "C" const char* srbh_last_error(void) { return g_err; }
 
 extern "C" size_t srbh_act16_bytes(int B, int C, int H, int W) {

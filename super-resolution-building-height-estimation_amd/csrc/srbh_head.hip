@@ -760,6 +760,15 @@ extern "C" int srbh_hpack_conv_h16_many(const srbh_hpack_desc* table_dev, int n,
     return SRBH_OK;
 }
 
+// Workgroup caps of the persistent tile walks (read from the environment at first use): the launch code below and srbh_head_wgs_cap
+// (srbh_aux.hip) both ask these, so a test can tell how many tiles a workgroup walks at a given shape.
+namespace srbh {
+int hconv16_wgs_cap() { static const int v = getenv("SRBH_HCONV16_WGS") ? atoi(getenv("SRBH_HCONV16_WGS")) : 768; return v; }
+int hconv_up_wgs_cap() { static const int v = getenv("SRBH_HCONV_UP_WGS") ? atoi(getenv("SRBH_HCONV_UP_WGS")) : 768; return v; }
+int hconv_entry_wgs_cap() { static const int v = getenv("SRBH_HCONV_ENTRY_WGS") ? atoi(getenv("SRBH_HCONV_ENTRY_WGS")) : 768; return v; }
+int hblock16_wgs_cap() { static const int v = getenv("SRBH_HBLOCK16_WGS") ? atoi(getenv("SRBH_HBLOCK16_WGS")) : 512; return v; }
+}  // namespace srbh
+
 static int hconv_impl(const srbh_hconv_args* a, void* stream, const int opt) {
     const bool h16 = opt != 0;
     SRBH_REQUIRE(a && a->src0 && a->w && a->out, "srbh_hconv_f32: null pointer");
@@ -823,7 +832,7 @@ static int hconv_impl(const srbh_hconv_args* a, void* stream, const int opt) {
                      !a->stats && !a->post_scale && !a->post_relu && !a->post_lrelu && !a->bstat_c && srbh_hconv_up_supported(H, W) && (p.ld0 & 3) == 0 &&
                      ((uintptr_t)a->src0 & (s16 ? 7 : 15)) == 0 && ((uintptr_t)a->out & (o16u ? 7 : 15)) == 0 && (a->io_h16 & ~(SRBH_IO_SRC0_H16 | SRBH_IO_OUT_H16)) == 0,
                      "srbh_hconv_h16: pixelshuffle2 == 2 (sub-pixel-major pack) is the fp16 16 -> 64 3x3 form without pre / post ops, W %% 64 == 0, H %% 4 == 0");
-        static const int up_wgs = getenv("SRBH_HCONV_UP_WGS") ? atoi(getenv("SRBH_HCONV_UP_WGS")) : 768;
+        const int up_wgs = hconv_up_wgs_cap();
         p.tiles_x = W / 64;
         p.tiles_per_img = p.tiles_x * (H / 4);
         p.ntiles = p.tiles_per_img * B;
@@ -839,7 +848,7 @@ static int hconv_impl(const srbh_hconv_args* a, void* stream, const int opt) {
         return SRBH_OK;
     }
     // the dominant layer shape has its own persistent, double-buffered kernel (srbh_hconv16_kernel.h)
-    static const int k16_wgs = getenv("SRBH_HCONV16_WGS") ? atoi(getenv("SRBH_HCONV16_WGS")) : 768;     // 0 = always the template
+    const int k16_wgs = hconv16_wgs_cap();     // 0 = always the template
     const bool src16 = (a->io_h16 & SRBH_IO_SRC0_H16) != 0, o16 = (a->io_h16 & SRBH_IO_OUT_H16) != 0, r16 = (a->io_h16 & SRBH_IO_RES1_H16) != 0;
     const bool full16 = a->cout == 16 && (p.out_ld & 3) == 0 && (p.out_coff & 3) == 0 && ((uintptr_t)a->out & (o16 ? 7 : 15)) == 0;
     const bool narrow = a->cout < 16 && !a->stats && !a->res1 && !o16;         // conv_last (1 / 7 channels): scalar stores
@@ -913,7 +922,7 @@ extern "C" int srbh_hconv_h16(const srbh_hconv_args* a, int bf16, void* stream) 
 // (srbh_hconv_entry_kernel.h), otherwise the two template launches -- the results are the same either way.
 extern "C" int srbh_hconv_entry_h16(const srbh_hconv_args* c1, const srbh_hconv_args* ds, int bf16, void* stream) {
     SRBH_REQUIRE(c1 && ds, "srbh_hconv_entry_h16: null arguments");
-    static const int wgs = getenv("SRBH_HCONV_ENTRY_WGS") ? atoi(getenv("SRBH_HCONV_ENTRY_WGS")) : 768;      // 0 = never fuse
+    const int wgs = hconv_entry_wgs_cap();      // 0 = never fuse
     const int cin = c1->c0 + c1->c1;
     const int ld0 = c1->src0_ld > 0 ? c1->src0_ld : c1->c0, ld1 = c1->src1_ld > 0 ? c1->src1_ld : c1->c1;
     const int dld0 = ds->src0_ld > 0 ? ds->src0_ld : ds->c0, dld1 = ds->src1_ld > 0 ? ds->src1_ld : ds->c1;
@@ -999,7 +1008,7 @@ extern "C" int srbh_hblock16_eval(const srbh_hblock16_args* a, void* stream) {
     SRBH_REQUIRE(a->B > 0 && srbh_hblock16_supported(a->H, a->W), "srbh_hblock16_eval: W %% 64 == 0 and H %% 4 == 0 (srbh_hblock16_supported)");
     SRBH_REQUIRE(((uintptr_t)a->x & 7) == 0 && (((uintptr_t)a->w1 | (uintptr_t)a->w2) & 7) == 0 && ((uintptr_t)a->out & (a->out_h16 ? 7 : 15)) == 0 &&
                  (((uintptr_t)a->scale1 | (uintptr_t)a->shift1 | (uintptr_t)a->scale2 | (uintptr_t)a->shift2) & 15) == 0, "srbh_hblock16_eval: misaligned tensor");
-    static const int wgs = getenv("SRBH_HBLOCK16_WGS") ? atoi(getenv("SRBH_HBLOCK16_WGS")) : 512;      // two per CU
+    const int wgs = hblock16_wgs_cap();      // two per CU
     HBlkParams p;
     p.x = a->x; p.w1 = a->w1; p.w2 = a->w2; p.s1 = a->scale1; p.h1 = a->shift1; p.s2 = a->scale2; p.h2 = a->shift2; p.out = a->out;
     p.B = a->B; p.H = a->H; p.W = a->W;

@@ -1320,6 +1320,12 @@ int grid_for(long n) {
 
 }  // namespace
 
+// workgroup caps of the two persistent gradient walks (srbh_internal.h; srbh_head_wgs_cap reports them)
+namespace srbh {
+int hwgrad16_wgs_cap() { static const int v = getenv("SRBH_HWGRAD16_WGS") ? atoi(getenv("SRBH_HWGRAD16_WGS")) : 768; return v; }
+int hbwd16_wgs_cap() { static const int v = getenv("SRBH_HBWD16_WGS") ? atoi(getenv("SRBH_HBWD16_WGS")) : 512; return v; }
+}  // namespace srbh
+
 namespace {
 int wgrad_impl(const srbh_hwgrad_args* a, void* stream, bool b16, const char* who) {
     SRBH_REQUIRE(a && a->src0 && a->dy && a->dw, "%s: null pointer", who);
@@ -1352,7 +1358,7 @@ int wgrad_impl(const srbh_hwgrad_args* a, void* stream, bool b16, const char* wh
     const bool can16 = (a->c0 & 3) == 0 && (a->c1 & 3) == 0 && (p.ld0 & 3) == 0 && (a->c1 == 0 || (p.ld1 & 3) == 0) && (a->cout & 15) == 0 &&
                        ((uintptr_t)a->src0 & 15) == 0 && ((uintptr_t)a->src1 & 15) == 0 && ((uintptr_t)a->dy & (ds16 ? 7 : 15)) == 0;
     // the dominant layer shape has its own double-buffered kernel (srbh_hwgrad16_kernel.h)
-    static const int k16_wgs = getenv("SRBH_HWGRAD16_WGS") ? atoi(getenv("SRBH_HWGRAD16_WGS")) : 768;   // 0 = never
+    const int k16_wgs = hwgrad16_wgs_cap();   // 0 = never
     const bool narrow = a->cout < 16 && !ds16;          // conv_last (1 / 7 output channels): zero-padded to one 16-channel block while staged
     const bool k16 = b16 && k16_wgs >= 8 && k16_wgs <= WS_SLOTS && a->ksize == 3 && a->c0 == 16 && a->c1 == 0 && (a->cout == 16 || narrow) &&
                      (a->W & 63) == 0 && (a->H & 3) == 0 && (p.ld0 & 3) == 0 && ((uintptr_t)a->src0 & (xs16 ? 7 : 15)) == 0 &&
@@ -1584,7 +1590,7 @@ extern "C" int srbh_hbwd16(const srbh_hbwd16_args* a, void* stream) {
     p.tiles_per_img = p.tiles_x * (a->H / 4);
     p.ntiles = p.tiles_per_img * a->B;
     p.tiles_per_xcd = (p.ntiles + 7) / 8;
-    static const int wgs = getenv("SRBH_HBWD16_WGS") ? atoi(getenv("SRBH_HBWD16_WGS")) : 512;
+    const int wgs = hbwd16_wgs_cap();
     SRBH_REQUIRE(wgs >= 8 && wgs <= WS_SLOTS, "SRBH_HBWD16_WGS must be 8 .. %d", WS_SLOTS);
     const int per_xcd = p.tiles_per_xcd < wgs / 8 ? p.tiles_per_xcd : wgs / 8;
     const int gx = per_xcd * 8;

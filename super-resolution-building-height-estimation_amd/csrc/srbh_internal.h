@@ -23,6 +23,14 @@ enum PathCounter { PATH_HCONV16 = 0, PATH_HCONV_TEMPLATE, PATH_ENTRY_FUSED, PATH
                    PATH_WGRAD_F32, PATH_WGRAD_ENTRY_FUSED, PATH_WGRAD_ENTRY_SPLIT, PATH_HCONV_UP, PATH_HBWD16, PATH_HBLOCK16, PATH_N };
 extern unsigned long long g_path_counters[PATH_N];
 inline void count_path(int i) { ++g_path_counters[i]; }
+// Workgroup caps of the head kernels' persistent tile walks (SRBH_*_WGS, read once): a walk launches min(tiles_per_xcd, cap / 8) workgroups
+// per XCD.  Defined next to the launch code that uses them (srbh_head.hip, srbh_head_bwd.hip); srbh_head_wgs_cap reports them.
+int hconv16_wgs_cap();
+int hconv_up_wgs_cap();
+int hconv_entry_wgs_cap();
+int hblock16_wgs_cap();
+int hwgrad16_wgs_cap();
+int hbwd16_wgs_cap();
 // Stream-ordered zero fill of `bytes` (a multiple of 4) by a KERNEL.  Not hipMemsetAsync: captured into a HIP graph, a memset node is
 // not kept in order with the kernels of the previous replay of the same graph (srbh_ptrunk.hip, ptrunk_reset_kernel), and every
 // libsrbh call must stay correct inside back-to-back graph replays (harness.TrainStep(graph=True), predict_tiles).
