@@ -1,5 +1,5 @@
 // srbh_hbwd16_kernel.h -- the backward of one 3x3, 16 -> 16 convolution of a BasicBlock behind its BatchNorm, as ONE pass (round 5).
-// Included by srbh_head_bwd.hip inside its anonymous namespace (after WG16T / bf16_pair / widen_b4 / NSLOT).
+// Included by srbh_head_bwd.hip inside its anonymous namespace (after WG16T / wg_row_taps / bf16_pair / widen_b4 / NSLOT).
 //
 // Reference graph (SR/HRfuse.py:142-159 through torch autograd): y = bn(conv(x')).  Given g = dL/dy, the three consumers of
 //      dc = coef * (g' - k1 - xhat * k2),   g' = g [masked by the ReLU behind the BatchNorm],  xhat = (c - mean) * invstd
@@ -250,20 +250,9 @@ __global__ __launch_bounds__(256, 2) void hbwd16_kernel(const HBParams p) {
         // ---- weight gradient: 4 pixel groups x 3 rows x 3 shifts (hwgrad16_kernel's loop)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const uint2w a2w = *(const uint2w*)(stage + abase + g * 8);
-            const short4w a = __builtin_bit_cast(short4w, a2w);
+            const short4w a = wg_frag(stage + abase + g * 8);
 #pragma unroll
-            for (int dy = 0; dy < 3; ++dy) {
-                const unsigned* rp = stage + bbase + dy * QX * 2 + g * 8;
-                const uint2w cur = *(const uint2w*)rp;
-                const unsigned pv = rp[-1], nx = rp[2];
-                const unsigned mid = __builtin_amdgcn_alignbit(cur[1], cur[0], 16);
-                const uint2w b0 = {__builtin_amdgcn_alignbit(cur[0], pv, 16), mid};
-                const uint2w b2 = {mid, __builtin_amdgcn_alignbit(nx, cur[1], 16)};
-                accw[dy * 3 + 0] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, __builtin_bit_cast(short4w, b0), accw[dy * 3 + 0], 0, 0, 0);
-                accw[dy * 3 + 1] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, __builtin_bit_cast(short4w, cur), accw[dy * 3 + 1], 0, 0, 0);
-                accw[dy * 3 + 2] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, __builtin_bit_cast(short4w, b2), accw[dy * 3 + 2], 0, 0, 0);
-            }
+            for (int dy = 0; dy < 3; ++dy) wg_row_taps(stage + bbase + dy * QX * 2 + g * 8, a, accw[dy * 3 + 0], accw[dy * 3 + 1], accw[dy * 3 + 2]);
         }
         // ---- data gradient: 9 taps x 4 pixel groups (hconv16_kernel's loop, bf16 operands)
         floatx4 acc[4];

@@ -1,9 +1,15 @@
 // srbh_head_bwd.hip -- backward kernels of the HR feature / fusion head (training: SURVEY.md 3.1, train.py:254-256).
 //
 // The reference gets these from torch autograd over SR/HRfuse.py; here each is a hand-written gfx950 kernel:
-//  * hwgrad_f32_kernel : weight gradient of a 3x3 / 1x1 conv as a GEMM over pixels on the fp32 matrix cores
-//                        dW[oc][ci][tap] = sum_px dY[px][oc] * X[px + tap][ci]   (v_mfma_f32_16x16x4_f32, K = 4 pixels),
-//                        X read with the same concat / folded BN+ReLU transform as the forward conv.
+//  * weight gradients of the 3x3 / 1x1 convs as a GEMM over pixels, dW[oc][ci][tap] = sum_px dY[px][oc] * X[px + tap][ci], X read with
+//    the same concat / folded BN+ReLU transform as the forward conv:
+//      - hwgrad_f32_kernel (here): fp32 matrix cores (v_mfma_f32_16x16x4_f32, K = 4 pixels), any channel counts;
+//      - srbh_hwgrad_b16_kernel.h: the bf16-operand kernels on 8 x 64 tiles (hwgrad_b16_kernel, hwgrad_entry_b16_kernel,
+//        hwgrad_ob_b16_kernel, hwgrad_entry64_b16_kernel) and the walk / staging / tap / flush pieces they share;
+//      - srbh_hwgrad16_kernel.h: the double-buffered 16 -> 16 kernel; srbh_hbwd16_kernel.h: that layer's data and weight gradient
+//        behind its BatchNorm backward in one pass;
+//    every workgroup stores its partial sums, the reduce kernels here add them in a fixed order (now, or batched: srbh_hwgrad_defer);
+//  * the host side of those: WGParams fillers, the kernel-form selection and launch of every weight-gradient entry point;
 //  * data gradients reuse the forward conv kernel (srbh_hconv_f32) with transposed + flipped weights
 //    (srbh_hpack_conv_f32(transpose_flip=1)).
 //  * BatchNorm backward in three steps: per-channel reductions (sum dy, sum dy*xhat) -> per-channel constants ->
@@ -73,6 +79,8 @@ __device__ __forceinline__ unsigned b16_field_pair(const float2w a, const float2
     const unsigned wa = ua[j >> 1], wb = ub[j >> 1];
     return (j & 1) ? ((wa >> 16) | (wb & 0xffff0000u)) : ((wa & 0xffffu) | (wb << 16));
 }
+
+#include "srbh_hwgrad_b16_kernel.h"
 
 // One workgroup walks tiles t = blockIdx.x, +gridDim.x, ... and keeps the 16(oc) x 16(ci) x taps partial sums of
 // one (oc block = blockIdx.y, ci chunk) in registers; flushed once per chunk through LDS with one atomic per value.
@@ -247,704 +255,6 @@ __global__ __launch_bounds__(256) void hwgrad_f32_kernel(const WGParams p) {
             // gradient order-dependent); every workgroup stores its partial, a second tiny kernel adds them in order
             p.ws[(((long)blockIdx.x * gridDim.y + ob) * nchunk + c) * (TAPS * 256) + u] = v;
         }
-    }
-}
-
-// ---- 16-bit-operand weight gradient (mixed-precision training: hrfuse.set_head_precision("f16")) ----------------------------------
-// Same GEMM over pixels, same tile walk, workspace and deterministic two-stage reduction as hwgrad_f32_kernel, but the products run
-// on v_mfma_f32_16x16x16_bf16 (K = 16 pixels per instruction; the fp32 form's K = 4 at 32 cycles made the fp32 kernel MFMA-bound at
-// ~2x its HBM time).  Both operands are rounded to bf16 (RNE) while staged -- dY needs bf16's exponent range, see srbh_head.hip --
-// and accumulated in fp32.  K is the pixel axis, so the 16-bit operands must be contiguous along PIXELS: the staging transposes
-// 4 pixels x 4 channels in registers and writes channel-major rows ([channel][row][pixel], 2 pixels per dword; channel stride
-// = 4 mod 64 dwords: the 8-byte fragment reads and the staging writes are bank-conflict free).  A tap's dx = -1/+1 fragments are
-// funnel-shifted (v_alignbit) out of the aligned quad and one dword of its neighbour.
-typedef short short4w __attribute__((ext_vector_type(4)));
-typedef unsigned uint2w __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned bf16_pair(float lo, float hi) { return bf16x2_rne(lo, hi); }
-
-template <int KS>
-struct WG16 {
-    static constexpr int TAPS = KS * KS, HALO = KS / 2;
-    static constexpr int ROWS = HT_H + 2 * HALO;
-    static constexpr int QX = KS == 3 ? 18 : 16;       // staged 4-pixel groups per row: image columns X0-4 .. X0+67 (3x3) / X0 .. X0+63
-    static constexpr int XOFF = KS == 3 ? 4 : 0;       // staged column of image column X0
-    static constexpr int SX = KS == 3 ? 388 : 260;     // dwords per staged X channel (>= ROWS*QX*2, = 4 mod 64)
-    static constexpr int SD = 260;                     // dwords per staged dY channel (8 rows x 64 pixels / 2 + 4)
-    static constexpr int LDS_B = (16 * SX + 16 * SD) * 4;   // >= the flush buffer (4 waves x TAPS x 256 floats)
-    static constexpr int LDS_B2 = (16 * SX + 32 * SD) * 4;  // + the second dY tile of the fused block-entry form (>= 4 x (TAPS + 1) x 256 floats)
-};
-
-// DS = 1: dY holds bf16 elements in memory (an internal gradient tensor of the training step): its bits are the operand
-// XM = 1: both tensors are ACT16 chunk planes (WGParams::x_* / dy_*): X fp16, dY bf16 (DS must be 1)
-// D2 = 1 (KS = 3, XM = 0): fused BasicBlock entry (SR/HRfuse.py:142-159): conv1 (3x3) and downsample[0] (1x1) read the same input, so
-//   their weight gradients share the staged X tile -- the 1x1 gradient is one more MFMA per K step on the centre-tap fragment with its
-//   own dY (p.dy2, same element type and channel count as dy); what bounds these kernels is the X staging (fp32 / fp16 -> bf16, 4x4
-//   register transposes into channel-major rows), which the separate 1x1 launch repeated in full.
-template <int KS, int DS, int XM = 0, int D2 = 0>
-__global__ __launch_bounds__(256) void hwgrad_b16_kernel(const WGParams p) {
-    static_assert(D2 == 0 || (KS == 3 && XM == 0), "the fused entry form is the 3x3 NHWC kernel");
-    extern __shared__ __attribute__((aligned(16))) float wsm[];
-    using G = WG16<KS>;
-    constexpr int TAPS = G::TAPS, HALO = G::HALO, ROWS = G::ROWS, QX = G::QX, SX = G::SX, SD = G::SD;
-    static_assert(G::LDS_B >= 4 * TAPS * 256 * 4, "flush buffer must fit");
-    unsigned* s_x = (unsigned*)wsm;                 // [16 ci][SX]
-    unsigned* s_dy = s_x + 16 * SX;                 // [16 oc][SD]
-    unsigned* s_dy2 = s_dy + 16 * SD;               // [16 oc][SD] (D2)
-    float* s_red = wsm;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l15 = lane & 15, kk = lane >> 4;
-    const int cin = p.c0 + p.c1;
-    const int nchunk = (cin + 15) / 16;
-    const int ob = blockIdx.y;
-    // (zchunk: with few tiles -- the RRDBNet training path at batch 8 has 64 -- the chunk loop is spread over blockIdx.z: a workgroup's
-    //  chunk iterations are a serial load -> LDS -> MFMA chain of ~4 us each, 12 of them for a 192-channel conv on a quarter-filled GPU)
-    const int c_lo = p.zchunk ? (int)blockIdx.z : 0, c_hi = p.zchunk ? (int)blockIdx.z + 1 : nchunk;
-
-    for (int c = c_lo; c < c_hi; ++c) {
-        floatx4 acc[TAPS];
-#pragma unroll
-        for (int tp = 0; tp < TAPS; ++tp) acc[tp] = floatx4{0.f, 0.f, 0.f, 0.f};
-        floatx4 acc2 = {0.f, 0.f, 0.f, 0.f};
-        // XCD-aware walk (see hconv_f32_kernel): XCD x = blockIdx % 8 owns the contiguous tiles [x*per_xcd, (x+1)*per_xcd), its
-        // gridDim/8 workgroups sweep them side by side, so the tiles' shared halo rows are re-read from that XCD's L2
-        const int t_end = min((int)(blockIdx.x & 7) * p.tiles_per_xcd + p.tiles_per_xcd, p.ntiles);
-        for (int t = (blockIdx.x & 7) * p.tiles_per_xcd + (blockIdx.x >> 3); t < t_end; t += gridDim.x >> 3) {
-            const int img = t / p.tiles_per_img;
-            const int trem = t - img * p.tiles_per_img;
-            const int ty = trem / p.tiles_x, tx = trem - ty * p.tiles_x;
-            const int Y0 = ty * HT_H, X0 = tx * HT_W;
-            // ---- stage: every global load of the tile is issued before the first LDS store.  (Issuing the NEXT tile's loads before this
-            // tile's MFMAs -- a software pipeline over the walk -- needs 281 registers, one workgroup per CU: 152 -> 232 us.)
-            constexpr int NIX = (ROWS * QX * 4 + 255) / 256, NID = HT_H * 16 * 4 / 256;
-            typedef typename std::conditional<DS != 0, float2w, floatx4>::type ldv_t;
-            floatx4 lx[NIX][4];
-            ldv_t ld[NID][4];
-            ldv_t ld2[D2 ? NID : 1][4];
-#pragma unroll
-            for (int it = 0; it < NIX; ++it) {
-                const int u = tid + it * 256;
-                const int cg = u & 3, q = u >> 2;
-                const int r = q / QX, qc = q - r * QX;
-                const int y = Y0 + r - HALO, x0 = X0 - G::XOFF + qc * 4;
-                const int ch = c * 16 + cg * 4;
-                const bool rowok = u < ROWS * QX * 4 && y >= 0 && y < p.H && ch < cin;
-                const long rowbase = ((long)img * p.H + y) * p.W;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    floatx4 a = {0.f, 0.f, 0.f, 0.f};
-                    const int x = x0 + i;
-                    if (rowok && x >= 0 && x < p.W) {
-                        if constexpr (XM != 0) {
-                            a = widen_h4(*(const float2w*)((const char*)p.src0 + (long)img * p.x_img_b + (long)(ch >> 5) * p.x_plane_b +
-                                                          (long)(y + 1) * p.x_row_b + (x + 1) * 64 + (ch & 31) * 2));
-                        } else if (ch < p.c0) {
-                            if (p.io & SRBH_WG_SRC0_H16)     // (uniform: fp16 elements in memory, e.g. RRDBNet features handed over as fp16)
-                                a = widen_h4(*(const float2w*)((const short*)p.src0 + (rowbase + x) * p.ld0 + ch));
-                            else
-                                a = *(const floatx4*)(p.src0 + (rowbase + x) * p.ld0 + ch);
-                            if (p.pre_scale) a = a * *(const floatx4*)(p.pre_scale + ch) + *(const floatx4*)(p.pre_shift + ch);
-                            if (p.pre_relu) {
-#pragma unroll
-                                for (int j = 0; j < 4; ++j) a[j] = fmaxf(a[j], 0.f);
-                            }
-                        } else {
-                            a = *(const floatx4*)(p.src1 + (rowbase + x) * p.ld1 + (ch - p.c0));
-                        }
-                    }
-                    lx[it][i] = a;
-                }
-            }
-#pragma unroll
-            for (int it = 0; it < NID; ++it) {
-                const int u = tid + it * 256;
-                const int cg = u & 3, q = u >> 2;
-                const int y = Y0 + (q >> 4), x0 = X0 + (q & 15) * 4;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    ldv_t a = ldv_t{};
-                    if (y < p.H && x0 + i < p.W) {
-                        if constexpr (XM != 0) {
-                            const int dch = p.dy_ch0 + ob * 16 + cg * 4;
-                            a = *(const ldv_t*)((const char*)p.dy + (long)img * p.dy_img_b + (long)(dch >> 5) * p.dy_plane_b + (long)(y + 1) * p.dy_row_b +
-                                                (x0 + i + 1) * 64 + (dch & 31) * 2);
-                        } else {
-                            a = *(const ldv_t*)((const char*)p.dy + ((((long)img * p.H + y) * p.W + x0 + i) * p.cout_total + ob * 16 + cg * 4) * (DS ? 2 : 4));
-                        }
-                    }
-                    ld[it][i] = a;
-                    if constexpr (D2 != 0) {
-                        ldv_t a2 = ldv_t{};
-                        if (y < p.H && x0 + i < p.W)
-                            a2 = *(const ldv_t*)((const char*)p.dy2 + ((((long)img * p.H + y) * p.W + x0 + i) * p.cout_total + ob * 16 + cg * 4) * (DS ? 2 : 4));
-                        ld2[it][i] = a2;
-                    }
-                }
-            }
-            __syncthreads();                       // the previous tile's fragment reads are done
-#pragma unroll
-            for (int it = 0; it < NIX; ++it) {
-                const int u = tid + it * 256;
-                if (u < ROWS * QX * 4) {
-                    const int cg = u & 3, q = u >> 2;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        *(uint2w*)(s_x + (cg * 4 + j) * SX + q * 2) =
-                            uint2w{bf16_pair(lx[it][0][j], lx[it][1][j]), bf16_pair(lx[it][2][j], lx[it][3][j])};
-                }
-            }
-#pragma unroll
-            for (int it = 0; it < NID; ++it) {
-                const int u = tid + it * 256;
-                const int cg = u & 3, q = u >> 2;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if constexpr (DS != 0)
-                        *(uint2w*)(s_dy + (cg * 4 + j) * SD + q * 2) = uint2w{b16_field_pair(ld[it][0], ld[it][1], j), b16_field_pair(ld[it][2], ld[it][3], j)};
-                    else
-                        *(uint2w*)(s_dy + (cg * 4 + j) * SD + q * 2) =
-                            uint2w{bf16_pair(ld[it][0][j], ld[it][1][j]), bf16_pair(ld[it][2][j], ld[it][3][j])};
-                    if constexpr (D2 != 0) {
-                        if constexpr (DS != 0)
-                            *(uint2w*)(s_dy2 + (cg * 4 + j) * SD + q * 2) = uint2w{b16_field_pair(ld2[it][0], ld2[it][1], j), b16_field_pair(ld2[it][2], ld2[it][3], j)};
-                        else
-                            *(uint2w*)(s_dy2 + (cg * 4 + j) * SD + q * 2) =
-                                uint2w{bf16_pair(ld2[it][0][j], ld2[it][1][j]), bf16_pair(ld2[it][2][j], ld2[it][3][j])};
-                    }
-                }
-            }
-            __syncthreads();
-            // ---- 2 rows x 4 groups of 16 pixels per wave
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) {
-                const int row = wave * 2 + (ks >> 2), g = ks & 3;
-                const uint2w a2 = *(const uint2w*)(s_dy + l15 * SD + (row * 16 + g * 4 + kk) * 2);
-                const short4w a = __builtin_bit_cast(short4w, a2);
-                const unsigned* bp = s_x + l15 * SX + (row * QX + (G::XOFF >> 2) + g * 4 + kk) * 2;
-#pragma unroll
-                for (int dy = 0; dy < KS; ++dy) {
-                    const unsigned* rp = bp + dy * QX * 2;
-                    const uint2w cur = *(const uint2w*)rp;
-                    if constexpr (KS == 3) {
-                        const unsigned pv = rp[-1], nx = rp[2];
-                        const unsigned mid = __builtin_amdgcn_alignbit(cur[1], cur[0], 16);
-                        const uint2w b0 = {__builtin_amdgcn_alignbit(cur[0], pv, 16), mid};
-                        const uint2w b2 = {mid, __builtin_amdgcn_alignbit(nx, cur[1], 16)};
-                        acc[dy * 3 + 0] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, __builtin_bit_cast(short4w, b0), acc[dy * 3 + 0], 0, 0, 0);
-                        acc[dy * 3 + 1] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, __builtin_bit_cast(short4w, cur), acc[dy * 3 + 1], 0, 0, 0);
-                        acc[dy * 3 + 2] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, __builtin_bit_cast(short4w, b2), acc[dy * 3 + 2], 0, 0, 0);
-                        if constexpr (D2 != 0) {
-                            if (dy == 1) {
-                                const uint2w d2 = *(const uint2w*)(s_dy2 + l15 * SD + (row * 16 + g * 4 + kk) * 2);
-                                acc2 = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(short4w, d2), __builtin_bit_cast(short4w, cur), acc2, 0, 0, 0);
-                            }
-                        }
-                    } else {
-                        acc[0] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, __builtin_bit_cast(short4w, cur), acc[0], 0, 0, 0);
-                    }
-                }
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int tp = 0; tp < TAPS; ++tp)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) s_red[((wave * TAPS + tp) * 16 + kk * 4 + r) * 16 + l15] = acc[tp][r];
-        __syncthreads();
-        for (int u = tid; u < TAPS * 256; u += 256) {
-            const float v = s_red[u] + s_red[TAPS * 256 + u] + s_red[2 * TAPS * 256 + u] + s_red[3 * TAPS * 256 + u];
-            p.ws[(((long)blockIdx.x * gridDim.y + ob) * nchunk + c) * (TAPS * 256) + u] = v;
-        }
-        __syncthreads();                           // s_red aliases the staging buffers of the next chunk
-        if constexpr (D2 != 0) {                   // the 1x1 gradient's partial sums, in the layout of a ksize = 1 call
-#pragma unroll
-            for (int r = 0; r < 4; ++r) s_red[(wave * 16 + kk * 4 + r) * 16 + l15] = acc2[r];
-            __syncthreads();
-            p.ws2[(((long)blockIdx.x * gridDim.y + ob) * nchunk + c) * 256 + tid] = s_red[tid] + s_red[256 + tid] + s_red[512 + tid] + s_red[768 + tid];
-            __syncthreads();
-        }
-    }
-}
-
-// Fused BasicBlock-entry weight gradient with the CHUNK loop inside the tile walk (round 4).  hwgrad_b16_kernel<3, DS, 0, 1> walks all its
-// tiles once per 16-channel chunk of the input: the 64-channel entry (HRfeature: cin = 64, fp16 features) re-staged both dY tiles four times
-// and touched 32 bytes of every 128-byte pixel row per pass -- 891 us for 805 MB (0.11 of the HBM peak, profiles/r04p).  Here a tile's dY /
-// dY2 are staged once, the NC chunks of X follow one another through the same LDS buffer (chunk c + 1's global loads are issued before
-// chunk c's MFMAs: the rows' other three 32-byte quarters come out of L2 while they are hot), and NC x 10 accumulators stay in registers.
-// Same tile walk, same wave -> row assignment, same flush: every partial sum is the bit pattern the chunk-outer kernel writes.
-template <int DS, int NC>
-__global__ __launch_bounds__(256) void hwgrad_entry_b16_kernel(const WGParams p) {
-    extern __shared__ __attribute__((aligned(16))) float wsm[];
-    using G = WG16<3>;
-    constexpr int TAPS = G::TAPS, HALO = G::HALO, ROWS = G::ROWS, QX = G::QX, SX = G::SX, SD = G::SD;
-    unsigned* s_x = (unsigned*)wsm;                 // [16 ci][SX]
-    unsigned* s_dy = s_x + 16 * SX;                 // [16 oc][SD]
-    unsigned* s_dy2 = s_dy + 16 * SD;               // [16 oc][SD]
-    float* s_red = wsm;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l15 = lane & 15, kk = lane >> 4;
-    const int cin = p.c0 + p.c1;
-    const int ob = blockIdx.y;
-    floatx4 acc[NC][TAPS];
-    floatx4 acc2[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-#pragma unroll
-        for (int tp = 0; tp < TAPS; ++tp) acc[c][tp] = floatx4{0.f, 0.f, 0.f, 0.f};
-        acc2[c] = floatx4{0.f, 0.f, 0.f, 0.f};
-    }
-    constexpr int NIX = (ROWS * QX * 4 + 255) / 256, NID = HT_H * 16 * 4 / 256;
-    typedef typename std::conditional<DS != 0, float2w, floatx4>::type ldv_t;
-    const int t_end = min((int)(blockIdx.x & 7) * p.tiles_per_xcd + p.tiles_per_xcd, p.ntiles);
-    for (int t = (blockIdx.x & 7) * p.tiles_per_xcd + (blockIdx.x >> 3); t < t_end; t += gridDim.x >> 3) {
-        const int img = t / p.tiles_per_img;
-        const int trem = t - img * p.tiles_per_img;
-        const int ty = trem / p.tiles_x, tx = trem - ty * p.tiles_x;
-        const int Y0 = ty * HT_H, X0 = tx * HT_W;
-        floatx4 lx[NIX][4];
-        auto load_x = [&](const int c) {
-#pragma unroll
-            for (int it = 0; it < NIX; ++it) {
-                const int u = tid + it * 256;
-                const int cg = u & 3, q = u >> 2;
-                const int r = q / QX, qc = q - r * QX;
-                const int y = Y0 + r - HALO, x0 = X0 - G::XOFF + qc * 4;
-                const int ch = c * 16 + cg * 4;
-                const bool rowok = u < ROWS * QX * 4 && y >= 0 && y < p.H && ch < cin;
-                const long rowbase = ((long)img * p.H + y) * p.W;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    floatx4 a = {0.f, 0.f, 0.f, 0.f};
-                    const int x = x0 + i;
-                    if (rowok && x >= 0 && x < p.W) {
-                        if (ch < p.c0) {
-                            if (p.io & SRBH_WG_SRC0_H16)
-                                a = widen_h4(*(const float2w*)((const short*)p.src0 + (rowbase + x) * p.ld0 + ch));
-                            else
-                                a = *(const floatx4*)(p.src0 + (rowbase + x) * p.ld0 + ch);
-                            if (p.pre_scale) a = a * *(const floatx4*)(p.pre_scale + ch) + *(const floatx4*)(p.pre_shift + ch);
-                            if (p.pre_relu) {
-#pragma unroll
-                                for (int j = 0; j < 4; ++j) a[j] = fmaxf(a[j], 0.f);
-                            }
-                        } else {
-                            a = *(const floatx4*)(p.src1 + (rowbase + x) * p.ld1 + (ch - p.c0));
-                        }
-                    }
-                    lx[it][i] = a;
-                }
-            }
-        };
-        auto store_x = [&]() {
-#pragma unroll
-            for (int it = 0; it < NIX; ++it) {
-                const int u = tid + it * 256;
-                if (u < ROWS * QX * 4) {
-                    const int cg = u & 3, q = u >> 2;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        *(uint2w*)(s_x + (cg * 4 + j) * SX + q * 2) =
-                            uint2w{bf16_pair(lx[it][0][j], lx[it][1][j]), bf16_pair(lx[it][2][j], lx[it][3][j])};
-                }
-            }
-        };
-        {
-            ldv_t ld[NID][4], ld2[NID][4];
-            load_x(0);
-#pragma unroll
-            for (int it = 0; it < NID; ++it) {
-                const int u = tid + it * 256;
-                const int cg = u & 3, q = u >> 2;
-                const int y = Y0 + (q >> 4), x0 = X0 + (q & 15) * 4;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    ldv_t a = ldv_t{}, a2 = ldv_t{};
-                    if (y < p.H && x0 + i < p.W) {
-                        const long off = ((((long)img * p.H + y) * p.W + x0 + i) * p.cout_total + ob * 16 + cg * 4) * (DS ? 2 : 4);
-                        a = *(const ldv_t*)((const char*)p.dy + off);
-                        a2 = *(const ldv_t*)((const char*)p.dy2 + off);
-                    }
-                    ld[it][i] = a;
-                    ld2[it][i] = a2;
-                }
-            }
-            __syncthreads();                       // the previous tile's fragment reads are done
-            store_x();
-#pragma unroll
-            for (int it = 0; it < NID; ++it) {
-                const int u = tid + it * 256;
-                const int cg = u & 3, q = u >> 2;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if constexpr (DS != 0) {
-                        *(uint2w*)(s_dy + (cg * 4 + j) * SD + q * 2) = uint2w{b16_field_pair(ld[it][0], ld[it][1], j), b16_field_pair(ld[it][2], ld[it][3], j)};
-                        *(uint2w*)(s_dy2 + (cg * 4 + j) * SD + q * 2) = uint2w{b16_field_pair(ld2[it][0], ld2[it][1], j), b16_field_pair(ld2[it][2], ld2[it][3], j)};
-                    } else {
-                        *(uint2w*)(s_dy + (cg * 4 + j) * SD + q * 2) = uint2w{bf16_pair(ld[it][0][j], ld[it][1][j]), bf16_pair(ld[it][2][j], ld[it][3][j])};
-                        *(uint2w*)(s_dy2 + (cg * 4 + j) * SD + q * 2) = uint2w{bf16_pair(ld2[it][0][j], ld2[it][1][j]), bf16_pair(ld2[it][2][j], ld2[it][3][j])};
-                    }
-                }
-            }
-            __syncthreads();
-        }
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            if (c + 1 < NC) load_x(c + 1);          // (in flight under this chunk's MFMAs)
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) {
-                const int row = wave * 2 + (ks >> 2), g = ks & 3;
-                const uint2w a2 = *(const uint2w*)(s_dy + l15 * SD + (row * 16 + g * 4 + kk) * 2);
-                const short4w a = __builtin_bit_cast(short4w, a2);
-                const unsigned* bp = s_x + l15 * SX + (row * QX + (G::XOFF >> 2) + g * 4 + kk) * 2;
-#pragma unroll
-                for (int dy = 0; dy < 3; ++dy) {
-                    const unsigned* rp = bp + dy * QX * 2;
-                    const uint2w cur = *(const uint2w*)rp;
-                    const unsigned pv = rp[-1], nx = rp[2];
-                    const unsigned mid = __builtin_amdgcn_alignbit(cur[1], cur[0], 16);
-                    const uint2w b0 = {__builtin_amdgcn_alignbit(cur[0], pv, 16), mid};
-                    const uint2w b2 = {mid, __builtin_amdgcn_alignbit(nx, cur[1], 16)};
-                    acc[c][dy * 3 + 0] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, __builtin_bit_cast(short4w, b0), acc[c][dy * 3 + 0], 0, 0, 0);
-                    acc[c][dy * 3 + 1] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, __builtin_bit_cast(short4w, cur), acc[c][dy * 3 + 1], 0, 0, 0);
-                    acc[c][dy * 3 + 2] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, __builtin_bit_cast(short4w, b2), acc[c][dy * 3 + 2], 0, 0, 0);
-                    if (dy == 1) {
-                        const uint2w d2 = *(const uint2w*)(s_dy2 + l15 * SD + (row * 16 + g * 4 + kk) * 2);
-                        acc2[c] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(short4w, d2), __builtin_bit_cast(short4w, cur), acc2[c], 0, 0, 0);
-                    }
-                }
-            }
-            if (c + 1 < NC) {
-                __syncthreads();                   // every wave has read chunk c's fragments
-                store_x();
-                __syncthreads();
-            }
-        }
-    }
-    // flush, chunk by chunk, in the layout of the chunk-outer kernel
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        __syncthreads();
-#pragma unroll
-        for (int tp = 0; tp < TAPS; ++tp)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) s_red[((wave * TAPS + tp) * 16 + kk * 4 + r) * 16 + l15] = acc[c][tp][r];
-        __syncthreads();
-        for (int u = tid; u < TAPS * 256; u += 256) {
-            const float v = s_red[u] + s_red[TAPS * 256 + u] + s_red[2 * TAPS * 256 + u] + s_red[3 * TAPS * 256 + u];
-            p.ws[(((long)blockIdx.x * gridDim.y + ob) * NC + c) * (TAPS * 256) + u] = v;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 4; ++r) s_red[(wave * 16 + kk * 4 + r) * 16 + l15] = acc2[c][r];
-        __syncthreads();
-        p.ws2[(((long)blockIdx.x * gridDim.y + ob) * NC + c) * 256 + tid] = s_red[tid] + s_red[256 + tid] + s_red[512 + tid] + s_red[768 + tid];
-    }
-}
-
-// Weight gradient of a conv with ONE input chunk and NOB output blocks (the Upsampler's 16 -> 64 convs, SR/HRfuse.py:17-44: dY = the
-// PixelShuffle-inverted gradient, 64 channels): hwgrad_b16_kernel runs grid.y = NOB workgroups per tile, each staging the same X tile
-// (the fp32 -> bf16 4x4 register transposes that bound these kernels).  Here the X tile is staged once and the NOB dY blocks follow one
-// another through the dY buffer (block ob + 1's loads issued before block ob's MFMAs), NOB x 9 accumulators in registers.  Same walk,
-// wave -> row assignment, products and flush layout as the chunk-outer kernel with grid.y = NOB: bit-identical partial sums.
-template <int DS, int NOB>
-__global__ __launch_bounds__(256) void hwgrad_ob_b16_kernel(const WGParams p) {
-    extern __shared__ __attribute__((aligned(16))) float wsm[];
-    using G = WG16<3>;
-    constexpr int TAPS = G::TAPS, HALO = G::HALO, ROWS = G::ROWS, QX = G::QX, SX = G::SX, SD = G::SD;
-    unsigned* s_x = (unsigned*)wsm;                 // [16 ci][SX]
-    unsigned* s_dy = s_x + 16 * SX;                 // [16 oc][SD]
-    float* s_red = wsm;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l15 = lane & 15, kk = lane >> 4;
-    const int cin = p.c0;
-    floatx4 acc[NOB][TAPS];
-#pragma unroll
-    for (int ob = 0; ob < NOB; ++ob)
-#pragma unroll
-        for (int tp = 0; tp < TAPS; ++tp) acc[ob][tp] = floatx4{0.f, 0.f, 0.f, 0.f};
-    constexpr int NIX = (ROWS * QX * 4 + 255) / 256, NID = HT_H * 16 * 4 / 256;
-    typedef typename std::conditional<DS != 0, float2w, floatx4>::type ldv_t;
-    const int t_end = min((int)(blockIdx.x & 7) * p.tiles_per_xcd + p.tiles_per_xcd, p.ntiles);
-    for (int t = (blockIdx.x & 7) * p.tiles_per_xcd + (blockIdx.x >> 3); t < t_end; t += gridDim.x >> 3) {
-        const int img = t / p.tiles_per_img;
-        const int trem = t - img * p.tiles_per_img;
-        const int ty = trem / p.tiles_x, tx = trem - ty * p.tiles_x;
-        const int Y0 = ty * HT_H, X0 = tx * HT_W;
-        ldv_t ld[NID][4];
-        auto load_dy = [&](const int ob) {
-#pragma unroll
-            for (int it = 0; it < NID; ++it) {
-                const int u = tid + it * 256;
-                const int cg = u & 3, q = u >> 2;
-                const int y = Y0 + (q >> 4), x0 = X0 + (q & 15) * 4;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    ldv_t a = ldv_t{};
-                    if (y < p.H && x0 + i < p.W)
-                        a = *(const ldv_t*)((const char*)p.dy + ((((long)img * p.H + y) * p.W + x0 + i) * p.cout_total + ob * 16 + cg * 4) * (DS ? 2 : 4));
-                    ld[it][i] = a;
-                }
-            }
-        };
-        auto store_dy = [&]() {
-#pragma unroll
-            for (int it = 0; it < NID; ++it) {
-                const int u = tid + it * 256;
-                const int cg = u & 3, q = u >> 2;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if constexpr (DS != 0)
-                        *(uint2w*)(s_dy + (cg * 4 + j) * SD + q * 2) = uint2w{b16_field_pair(ld[it][0], ld[it][1], j), b16_field_pair(ld[it][2], ld[it][3], j)};
-                    else
-                        *(uint2w*)(s_dy + (cg * 4 + j) * SD + q * 2) = uint2w{bf16_pair(ld[it][0][j], ld[it][1][j]), bf16_pair(ld[it][2][j], ld[it][3][j])};
-                }
-            }
-        };
-        {
-            floatx4 lx[NIX][4];
-#pragma unroll
-            for (int it = 0; it < NIX; ++it) {
-                const int u = tid + it * 256;
-                const int cg = u & 3, q = u >> 2;
-                const int r = q / QX, qc = q - r * QX;
-                const int y = Y0 + r - HALO, x0 = X0 - G::XOFF + qc * 4;
-                const int ch = cg * 4;
-                const bool rowok = u < ROWS * QX * 4 && y >= 0 && y < p.H && ch < cin;
-                const long rowbase = ((long)img * p.H + y) * p.W;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    floatx4 a = {0.f, 0.f, 0.f, 0.f};
-                    const int x = x0 + i;
-                    if (rowok && x >= 0 && x < p.W) {
-                        if (p.io & SRBH_WG_SRC0_H16)
-                            a = widen_h4(*(const float2w*)((const short*)p.src0 + (rowbase + x) * p.ld0 + ch));
-                        else
-                            a = *(const floatx4*)(p.src0 + (rowbase + x) * p.ld0 + ch);
-                        if (p.pre_scale) a = a * *(const floatx4*)(p.pre_scale + ch) + *(const floatx4*)(p.pre_shift + ch);
-                        if (p.pre_relu) {
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) a[j] = fmaxf(a[j], 0.f);
-                        }
-                    }
-                    lx[it][i] = a;
-                }
-            }
-            load_dy(0);
-            __syncthreads();                       // the previous tile's fragment reads are done
-#pragma unroll
-            for (int it = 0; it < NIX; ++it) {
-                const int u = tid + it * 256;
-                if (u < ROWS * QX * 4) {
-                    const int cg = u & 3, q = u >> 2;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        *(uint2w*)(s_x + (cg * 4 + j) * SX + q * 2) =
-                            uint2w{bf16_pair(lx[it][0][j], lx[it][1][j]), bf16_pair(lx[it][2][j], lx[it][3][j])};
-                }
-            }
-            store_dy();
-            __syncthreads();
-        }
-#pragma unroll
-        for (int ob = 0; ob < NOB; ++ob) {
-            if (ob + 1 < NOB) load_dy(ob + 1);      // (in flight under this block's MFMAs)
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) {
-                const int row = wave * 2 + (ks >> 2), g = ks & 3;
-                const uint2w a2 = *(const uint2w*)(s_dy + l15 * SD + (row * 16 + g * 4 + kk) * 2);
-                const short4w a = __builtin_bit_cast(short4w, a2);
-                const unsigned* bp = s_x + l15 * SX + (row * QX + (G::XOFF >> 2) + g * 4 + kk) * 2;
-#pragma unroll
-                for (int dy = 0; dy < 3; ++dy) {
-                    const unsigned* rp = bp + dy * QX * 2;
-                    const uint2w cur = *(const uint2w*)rp;
-                    const unsigned pv = rp[-1], nx = rp[2];
-                    const unsigned mid = __builtin_amdgcn_alignbit(cur[1], cur[0], 16);
-                    const uint2w b0 = {__builtin_amdgcn_alignbit(cur[0], pv, 16), mid};
-                    const uint2w b2 = {mid, __builtin_amdgcn_alignbit(nx, cur[1], 16)};
-                    acc[ob][dy * 3 + 0] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, __builtin_bit_cast(short4w, b0), acc[ob][dy * 3 + 0], 0, 0, 0);
-                    acc[ob][dy * 3 + 1] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, __builtin_bit_cast(short4w, cur), acc[ob][dy * 3 + 1], 0, 0, 0);
-                    acc[ob][dy * 3 + 2] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, __builtin_bit_cast(short4w, b2), acc[ob][dy * 3 + 2], 0, 0, 0);
-                }
-            }
-            if (ob + 1 < NOB) {
-                __syncthreads();                   // every wave has read block ob's dY fragments
-                store_dy();
-                __syncthreads();
-            }
-        }
-    }
-#pragma unroll
-    for (int ob = 0; ob < NOB; ++ob) {
-        __syncthreads();
-#pragma unroll
-        for (int tp = 0; tp < TAPS; ++tp)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) s_red[((wave * TAPS + tp) * 16 + kk * 4 + r) * 16 + l15] = acc[ob][tp][r];
-        __syncthreads();
-        for (int u = tid; u < TAPS * 256; u += 256) {
-            const float v = s_red[u] + s_red[TAPS * 256 + u] + s_red[2 * TAPS * 256 + u] + s_red[3 * TAPS * 256 + u];
-            p.ws[((long)blockIdx.x * NOB + ob) * (TAPS * 256) + u] = v;          // (= the chunk-outer layout with grid.y = NOB, nchunk = 1)
-        }
-    }
-}
-
-// HRfeature's entry (cin = 64, the RRDBNet features handed over as fp16 NHWC: 128 bytes per pixel): the chunked kernels above read 32 bytes
-// of every pixel row per pass -- each load instruction touches 16 different 128-byte lines -- and ran at 0.11 of the HBM peak.  Here a lane
-// loads 16 bytes (8 channels) and 8 lanes cover a pixel's whole row, ALL FOUR chunks of a tile are staged at once (64 channel rows in LDS,
-// 130 KB with the two dY tiles: one workgroup per CU), and the next tile's global loads are issued before this tile's MFMAs (register
-// prefetch: 96 + 32 registers) -- the one workgroup per CU has nothing else to hide the load latency behind.  Same walk, wave -> row
-// assignment, products and flush as hwgrad_entry_b16_kernel<DS, 4>: bit-identical partial sums.
-struct WG64 {
-    using G = WG16<3>;
-    static constexpr int NIT = (G::ROWS * G::QX * 8 + 255) / 256;           // 16-byte units of the X tile per thread
-    static constexpr int LDS_B = (64 * G::SX + 32 * G::SD) * 4;
-};
-typedef unsigned uint4w __attribute__((ext_vector_type(4)));
-typedef _Float16 half8w __attribute__((ext_vector_type(8)));
-template <int DS>
-__global__ __launch_bounds__(256) void hwgrad_entry64_b16_kernel(const WGParams p) {
-    extern __shared__ __attribute__((aligned(16))) float wsm[];
-    using G = WG16<3>;
-    constexpr int TAPS = G::TAPS, ROWS = G::ROWS, QX = G::QX, SX = G::SX, SD = G::SD, NIT = WG64::NIT, NID = HT_H * 16 * 4 / 256, NC = 4;
-    static_assert(WG64::LDS_B >= 4 * TAPS * 256 * 4, "flush buffer must fit");
-    unsigned* s_x = (unsigned*)wsm;                 // [64 ci][SX]
-    unsigned* s_dy = s_x + 64 * SX;                 // [16 oc][SD]
-    unsigned* s_dy2 = s_dy + 16 * SD;
-    float* s_red = wsm;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l15 = lane & 15, kk = lane >> 4;
-    const int ob = blockIdx.y;
-    typedef typename std::conditional<DS != 0, float2w, floatx4>::type ldv_t;
-    floatx4 acc[NC][TAPS];
-    floatx4 acc2[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-#pragma unroll
-        for (int tp = 0; tp < TAPS; ++tp) acc[c][tp] = floatx4{0.f, 0.f, 0.f, 0.f};
-        acc2[c] = floatx4{0.f, 0.f, 0.f, 0.f};
-    }
-    uint4w lx[NIT][4];
-    ldv_t ld[NID][4], ld2[NID][4];
-    auto load_tile = [&](const int t) {
-        const int img = t / p.tiles_per_img;
-        const int trem = t - img * p.tiles_per_img;
-        const int ty = trem / p.tiles_x, tx = trem - ty * p.tiles_x;
-        const int Y0 = ty * HT_H, X0 = tx * HT_W;
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int u = tid + it * 256;
-            const int pc = u & 7, q = u >> 3;
-            const int r = q / QX, qc = q - r * QX;
-            const int y = Y0 + r - 1, x0 = X0 - G::XOFF + qc * 4;
-            const bool rowok = u < ROWS * QX * 8 && y >= 0 && y < p.H;
-            const short* rowp = (const short*)p.src0 + (((long)img * p.H + y) * p.W) * 64 + pc * 8;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                uint4w a = {0u, 0u, 0u, 0u};
-                const int x = x0 + i;
-                if (rowok && x >= 0 && x < p.W) a = *(const uint4w*)(rowp + (long)x * 64);
-                lx[it][i] = a;
-            }
-        }
-#pragma unroll
-        for (int it = 0; it < NID; ++it) {
-            const int u = tid + it * 256;
-            const int cg = u & 3, q = u >> 2;
-            const int y = Y0 + (q >> 4), x0 = X0 + (q & 15) * 4;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                ldv_t a = ldv_t{}, a2 = ldv_t{};
-                if (y < p.H && x0 + i < p.W) {
-                    const long off = ((((long)img * p.H + y) * p.W + x0 + i) * p.cout_total + ob * 16 + cg * 4) * (DS ? 2 : 4);
-                    a = *(const ldv_t*)((const char*)p.dy + off);
-                    a2 = *(const ldv_t*)((const char*)p.dy2 + off);
-                }
-                ld[it][i] = a;
-                ld2[it][i] = a2;
-            }
-        }
-    };
-    const int t_end = min((int)(blockIdx.x & 7) * p.tiles_per_xcd + p.tiles_per_xcd, p.ntiles);
-    const int t_step = gridDim.x >> 3;
-    int t = (blockIdx.x & 7) * p.tiles_per_xcd + (blockIdx.x >> 3);
-    if (t < t_end) load_tile(t);
-    for (; t < t_end; t += t_step) {
-        __syncthreads();                           // the previous tile's fragment reads are done
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int u = tid + it * 256;
-            if (u < ROWS * QX * 8) {
-                const int pc = u & 7, q = u >> 3;
-                const half8w h0 = __builtin_bit_cast(half8w, lx[it][0]), h1 = __builtin_bit_cast(half8w, lx[it][1]);
-                const half8w h2 = __builtin_bit_cast(half8w, lx[it][2]), h3 = __builtin_bit_cast(half8w, lx[it][3]);
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    *(uint2w*)(s_x + (pc * 8 + j) * SX + q * 2) =
-                        uint2w{bf16_pair((float)h0[j], (float)h1[j]), bf16_pair((float)h2[j], (float)h3[j])};
-            }
-        }
-#pragma unroll
-        for (int it = 0; it < NID; ++it) {
-            const int u = tid + it * 256;
-            const int cg = u & 3, q = u >> 2;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if constexpr (DS != 0) {
-                    *(uint2w*)(s_dy + (cg * 4 + j) * SD + q * 2) = uint2w{b16_field_pair(ld[it][0], ld[it][1], j), b16_field_pair(ld[it][2], ld[it][3], j)};
-                    *(uint2w*)(s_dy2 + (cg * 4 + j) * SD + q * 2) = uint2w{b16_field_pair(ld2[it][0], ld2[it][1], j), b16_field_pair(ld2[it][2], ld2[it][3], j)};
-                } else {
-                    *(uint2w*)(s_dy + (cg * 4 + j) * SD + q * 2) = uint2w{bf16_pair(ld[it][0][j], ld[it][1][j]), bf16_pair(ld[it][2][j], ld[it][3][j])};
-                    *(uint2w*)(s_dy2 + (cg * 4 + j) * SD + q * 2) = uint2w{bf16_pair(ld2[it][0][j], ld2[it][1][j]), bf16_pair(ld2[it][2][j], ld2[it][3][j])};
-                }
-            }
-        }
-        __syncthreads();
-        if (t + t_step < t_end) load_tile(t + t_step);      // in flight under this tile's 4 x 80 MFMAs
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) {
-                const int row = wave * 2 + (ks >> 2), g = ks & 3;
-                const uint2w a2 = *(const uint2w*)(s_dy + l15 * SD + (row * 16 + g * 4 + kk) * 2);
-                const short4w a = __builtin_bit_cast(short4w, a2);
-                const unsigned* bp = s_x + (c * 16 + l15) * SX + (row * QX + (G::XOFF >> 2) + g * 4 + kk) * 2;
-#pragma unroll
-                for (int dy = 0; dy < 3; ++dy) {
-                    const unsigned* rp = bp + dy * QX * 2;
-                    const uint2w cur = *(const uint2w*)rp;
-                    const unsigned pv = rp[-1], nx = rp[2];
-                    const unsigned mid = __builtin_amdgcn_alignbit(cur[1], cur[0], 16);
-                    const uint2w b0 = {__builtin_amdgcn_alignbit(cur[0], pv, 16), mid};
-                    const uint2w b2 = {mid, __builtin_amdgcn_alignbit(nx, cur[1], 16)};
-                    acc[c][dy * 3 + 0] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, __builtin_bit_cast(short4w, b0), acc[c][dy * 3 + 0], 0, 0, 0);
-                    acc[c][dy * 3 + 1] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, __builtin_bit_cast(short4w, cur), acc[c][dy * 3 + 1], 0, 0, 0);
-                    acc[c][dy * 3 + 2] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, __builtin_bit_cast(short4w, b2), acc[c][dy * 3 + 2], 0, 0, 0);
-                    if (dy == 1) {
-                        const uint2w d2 = *(const uint2w*)(s_dy2 + l15 * SD + (row * 16 + g * 4 + kk) * 2);
-                        acc2[c] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(short4w, d2), __builtin_bit_cast(short4w, cur), acc2[c], 0, 0, 0);
-                    }
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        __syncthreads();
-#pragma unroll
-        for (int tp = 0; tp < TAPS; ++tp)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) s_red[((wave * TAPS + tp) * 16 + kk * 4 + r) * 16 + l15] = acc[c][tp][r];
-        __syncthreads();
-        for (int u = tid; u < TAPS * 256; u += 256) {
-            const float v = s_red[u] + s_red[TAPS * 256 + u] + s_red[2 * TAPS * 256 + u] + s_red[3 * TAPS * 256 + u];
-            p.ws[(((long)blockIdx.x * gridDim.y + ob) * NC + c) * (TAPS * 256) + u] = v;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 4; ++r) s_red[(wave * 16 + kk * 4 + r) * 16 + l15] = acc2[c][r];
-        __syncthreads();
-        p.ws2[(((long)blockIdx.x * gridDim.y + ob) * NC + c) * 256 + tid] = s_red[tid] + s_red[256 + tid] + s_red[512 + tid] + s_red[768 + tid];
     }
 }
 
@@ -1327,12 +637,18 @@ int hbwd16_wgs_cap() { static const int v = getenv("SRBH_HBWD16_WGS") ? atoi(get
 }  // namespace srbh
 
 namespace {
-int wgrad_impl(const srbh_hwgrad_args* a, void* stream, bool b16, const char* who) {
-    SRBH_REQUIRE(a && a->src0 && a->dy && a->dw, "%s: null pointer", who);
-    SRBH_REQUIRE(a->c0 > 0 && a->c1 >= 0 && (a->c1 == 0 || a->src1), "srbh_hconv_wgrad: bad channel split");
-    SRBH_REQUIRE(a->ksize == 3 || a->ksize == 1, "srbh_hconv_wgrad: ksize must be 1 or 3");
-    SRBH_REQUIRE(a->cout >= 1 && a->cout <= 64 && a->B > 0 && a->H > 0 && a->W > 0, "srbh_hconv_wgrad: bad shape");
-    WGParams p;
+// tile geometry of a walk over th x 64 tiles (th = HT_H; 4: hwgrad16_kernel, whose shapes have whole tiles only)
+void wg_set_tiles(WGParams& p, int B, int H, int W, int th) {
+    p.B = B; p.H = H; p.W = W;
+    p.tiles_x = (W + HT_W - 1) / HT_W;
+    p.tiles_per_img = p.tiles_x * ((H + th - 1) / th);
+    p.ntiles = p.tiles_per_img * B;
+    p.tiles_per_xcd = (p.ntiles + 7) / 8;
+}
+// workgroup columns (grid.x) of the 8 x 64 walks: a multiple of 8 (the same number of workgroups per XCD), at most 512
+int wg_columns(const WGParams& p) { return p.ntiles < 512 ? (p.ntiles + 7) / 8 * 8 : 512; }
+// sources, folded BN and dY of an NHWC call
+void wg_set_tensors(WGParams& p, const srbh_hwgrad_args* a) {
     p.src0 = a->src0; p.src1 = a->src1; p.c0 = a->c0; p.c1 = a->c1;
     p.ld0 = a->src0_ld > 0 ? a->src0_ld : a->c0;
     p.ld1 = a->src1_ld > 0 ? a->src1_ld : a->c1;
@@ -1340,19 +656,32 @@ int wgrad_impl(const srbh_hwgrad_args* a, void* stream, bool b16, const char* wh
     p.dy = a->dy; p.cout_total = a->cout; p.dw = a->dw; p.ws = a->ws;
     p.io = a->io;
     p.zchunk = 0;
+}
+// one launch of a weight-gradient kernel with lds_bytes of dynamic LDS (its limit is raised once per device and kernel form)
+template <auto Kernel>
+int launch_wg(dim3 grid, int lds_bytes, hipStream_t st, const WGParams& p) {
+    SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)));
+    hipLaunchKernelGGL(Kernel, grid, dim3(256), lds_bytes, st, p);
+    SRBH_HIP(hipGetLastError());
+    return SRBH_OK;
+}
+
+int wgrad_impl(const srbh_hwgrad_args* a, void* stream, bool b16, const char* who) {
+    SRBH_REQUIRE(a && a->src0 && a->dy && a->dw, "%s: null pointer", who);
+    SRBH_REQUIRE(a->c0 > 0 && a->c1 >= 0 && (a->c1 == 0 || a->src1), "srbh_hconv_wgrad: bad channel split");
+    SRBH_REQUIRE(a->ksize == 3 || a->ksize == 1, "srbh_hconv_wgrad: ksize must be 1 or 3");
+    SRBH_REQUIRE(a->cout >= 1 && a->cout <= 64 && a->B > 0 && a->H > 0 && a->W > 0, "srbh_hconv_wgrad: bad shape");
+    WGParams p = {};
+    wg_set_tensors(p, a);
     SRBH_REQUIRE(a->ws, "srbh_hconv_wgrad: workspace missing (srbh_hwgrad_ws_bytes)");
     SRBH_REQUIRE((a->io & ~(SRBH_WG_SRC0_H16 | SRBH_WG_DY_B16)) == 0, "srbh_hconv_wgrad: unknown io bits");
     SRBH_REQUIRE(!a->io || b16, "srbh_hconv_wgrad_f32: 16-bit tensors in memory need the bf16-operand form (srbh_hconv_wgrad_b16)");
     const bool xs16 = (a->io & SRBH_WG_SRC0_H16) != 0, ds16 = (a->io & SRBH_WG_DY_B16) != 0;
-    p.B = a->B; p.H = a->H; p.W = a->W;
-    p.tiles_x = (a->W + HT_W - 1) / HT_W;
-    p.tiles_per_img = p.tiles_x * ((a->H + HT_H - 1) / HT_H);
-    p.ntiles = p.tiles_per_img * a->B;
+    wg_set_tiles(p, a->B, a->H, a->W, HT_H);
     hipStream_t st = (hipStream_t)stream;
     const int cin = a->c0 + a->c1;
     const int nob = (a->cout + 15) / 16;
-    int gx = p.ntiles < 512 ? (p.ntiles + 7) / 8 * 8 : 512;                // (a multiple of 8: the same number of workgroups per XCD)
-    p.tiles_per_xcd = (p.ntiles + 7) / 8;
+    int gx = wg_columns(p);
     // the bf16 form moves whole 4-channel groups with 16-byte loads and whole 16-channel output blocks; the few layers outside
     // that (the 1- and 7-channel output convs) keep the fp32 kernel
     const bool can16 = (a->c0 & 3) == 0 && (a->c1 & 3) == 0 && (p.ld0 & 3) == 0 && (a->c1 == 0 || (p.ld1 & 3) == 0) && (a->cout & 15) == 0 &&
@@ -1368,58 +697,35 @@ int wgrad_impl(const srbh_hwgrad_args* a, void* stream, bool b16, const char* wh
     SRBH_REQUIRE(!ds16 || k16 || can16, "srbh_hconv_wgrad_b16: a bf16 dY needs 4-aligned channels / 16-channel output blocks");
     count_path(k16 ? PATH_WGRAD16 : (b16 && can16) ? PATH_WGRAD_B16_GENERIC : PATH_WGRAD_F32);
     static const int ob_inner = getenv("SRBH_WGRAD_OB_INNER") ? atoi(getenv("SRBH_WGRAD_OB_INNER")) : 1;      // 0: grid.y = output blocks (A/B aid)
+    int rc;
     if (k16) {
-        p.tiles_x = a->W / 64;
-        p.tiles_per_img = p.tiles_x * (a->H / 4);
-        p.ntiles = p.tiles_per_img * a->B;
-        p.tiles_per_xcd = (p.ntiles + 7) / 8;
+        wg_set_tiles(p, a->B, a->H, a->W, 4);
         const int per_xcd = p.tiles_per_xcd < k16_wgs / 8 ? p.tiles_per_xcd : k16_wgs / 8;
         gx = per_xcd * 8;
-#define SRBH_WG16(X_, D_)                                                                                                              \
-    do {                                                                                                                          \
-        SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)hwgrad16_kernel<X_, D_>, hipFuncAttributeMaxDynamicSharedMemorySize, WG16T::LDS_B))); \
-        hipLaunchKernelGGL((hwgrad16_kernel<X_, D_>), dim3(gx), dim3(256), WG16T::LDS_B, st, p);                                   \
-    } while (0)
-        if (narrow && xs16) SRBH_WG16(1, 2);
-        else if (narrow) SRBH_WG16(0, 2);
-        else if (xs16 && ds16) SRBH_WG16(1, 1);
-        else if (xs16) SRBH_WG16(1, 0);
-        else if (ds16) SRBH_WG16(0, 1);
-        else SRBH_WG16(0, 0);
-#undef SRBH_WG16
-    } else
-    if (b16 && can16 && a->ksize == 3 && a->c1 == 0 && cin <= 16 && nob == 4 && ob_inner) {
+        const dim3 grid(gx);
+        constexpr int LDS_B = WG16T::LDS_B;
+        if (narrow && xs16) rc = launch_wg<hwgrad16_kernel<1, 2>>(grid, LDS_B, st, p);
+        else if (narrow) rc = launch_wg<hwgrad16_kernel<0, 2>>(grid, LDS_B, st, p);
+        else if (xs16 && ds16) rc = launch_wg<hwgrad16_kernel<1, 1>>(grid, LDS_B, st, p);
+        else if (xs16) rc = launch_wg<hwgrad16_kernel<1, 0>>(grid, LDS_B, st, p);
+        else if (ds16) rc = launch_wg<hwgrad16_kernel<0, 1>>(grid, LDS_B, st, p);
+        else rc = launch_wg<hwgrad16_kernel<0, 0>>(grid, LDS_B, st, p);
+    } else if (b16 && can16 && a->ksize == 3 && a->c1 == 0 && cin <= 16 && nob == 4 && ob_inner) {
         // one input chunk, four output blocks (the Upsampler's 16 -> 64 convs): X staged once per tile, the dY blocks inside the walk
-        if (ds16) {
-            SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)hwgrad_ob_b16_kernel<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, WG16<3>::LDS_B)));
-            hipLaunchKernelGGL((hwgrad_ob_b16_kernel<1, 4>), dim3(gx), dim3(256), WG16<3>::LDS_B, st, p);
-        } else {
-            SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)hwgrad_ob_b16_kernel<0, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, WG16<3>::LDS_B)));
-            hipLaunchKernelGGL((hwgrad_ob_b16_kernel<0, 4>), dim3(gx), dim3(256), WG16<3>::LDS_B, st, p);
-        }
-    } else
-    if (b16 && can16) {
-#define SRBH_WGB(K_, D_)                                                                                                               \
-    do {                                                                                                                          \
-        SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)hwgrad_b16_kernel<K_, D_>, hipFuncAttributeMaxDynamicSharedMemorySize, WG16<K_>::LDS_B))); \
-        hipLaunchKernelGGL((hwgrad_b16_kernel<K_, D_>), dim3(gx, nob), dim3(256), WG16<K_>::LDS_B, st, p);                          \
-    } while (0)
-        if (a->ksize == 3) {
-            if (ds16) SRBH_WGB(3, 1); else SRBH_WGB(3, 0);
-        } else {
-            if (ds16) SRBH_WGB(1, 1); else SRBH_WGB(1, 0);
-        }
-#undef SRBH_WGB
+        if (ds16) rc = launch_wg<hwgrad_ob_b16_kernel<1, 4>>(dim3(gx), WG16<3>::LDS_B, st, p);
+        else rc = launch_wg<hwgrad_ob_b16_kernel<0, 4>>(dim3(gx), WG16<3>::LDS_B, st, p);
+    } else if (b16 && can16) {
+        const dim3 grid(gx, nob);
+        if (a->ksize == 3 && ds16) rc = launch_wg<hwgrad_b16_kernel<3, 1>>(grid, WG16<3>::LDS_B, st, p);
+        else if (a->ksize == 3) rc = launch_wg<hwgrad_b16_kernel<3, 0>>(grid, WG16<3>::LDS_B, st, p);
+        else if (ds16) rc = launch_wg<hwgrad_b16_kernel<1, 1>>(grid, WG16<1>::LDS_B, st, p);
+        else rc = launch_wg<hwgrad_b16_kernel<1, 0>>(grid, WG16<1>::LDS_B, st, p);
     } else if (a->ksize == 3) {
-        constexpr int LDS_B = (10 * 66 * 16 + 4 * 9 * 256) * 4;   // X tile + max(dY tile, flush buffer)
-        SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)hwgrad_f32_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B)));
-        hipLaunchKernelGGL(hwgrad_f32_kernel<3>, dim3(gx, nob), dim3(256), LDS_B, st, p);
+        rc = launch_wg<hwgrad_f32_kernel<3>>(dim3(gx, nob), (10 * 66 * 16 + 4 * 9 * 256) * 4, st, p);   // X tile + max(dY tile, flush buffer)
     } else {
-        constexpr int LDS_B = (8 * 64 * 16 + 8 * 64 * 16) * 4;
-        SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)hwgrad_f32_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B)));
-        hipLaunchKernelGGL(hwgrad_f32_kernel<1>, dim3(gx, nob), dim3(256), LDS_B, st, p);
+        rc = launch_wg<hwgrad_f32_kernel<1>>(dim3(gx, nob), (8 * 64 * 16 + 8 * 64 * 16) * 4, st, p);
     }
-    SRBH_HIP(hipGetLastError());
+    if (rc) return rc;
     const int taps = a->ksize * a->ksize, nchunk = (cin + 15) / 16;
     const long U = (long)nob * nchunk * taps * 256;
     return reduce_partials(a->ws, a->dw, U, gx, nchunk, taps, a->cout, cin, st);
@@ -1452,45 +758,30 @@ extern "C" int srbh_hconv_wgrad_entry_b16(const srbh_hwgrad_args* a3, const srbh
     }
     count_path(PATH_WGRAD_ENTRY_FUSED);
     WGParams p = {};
-    p.src0 = a3->src0; p.src1 = a3->src1; p.c0 = a3->c0; p.c1 = a3->c1; p.ld0 = ld0; p.ld1 = ld1;
-    p.pre_scale = a3->pre_scale; p.pre_shift = a3->pre_shift; p.pre_relu = a3->pre_relu;
-    p.dy = a3->dy; p.cout_total = a3->cout; p.dw = a3->dw; p.ws = a3->ws; p.io = a3->io; p.zchunk = 0;
+    wg_set_tensors(p, a3);
     p.dy2 = a1->dy; p.ws2 = a1->ws;
-    p.B = a3->B; p.H = a3->H; p.W = a3->W;
-    p.tiles_x = (a3->W + HT_W - 1) / HT_W;
-    p.tiles_per_img = p.tiles_x * ((a3->H + HT_H - 1) / HT_H);
-    p.ntiles = p.tiles_per_img * a3->B;
-    p.tiles_per_xcd = (p.ntiles + 7) / 8;
+    wg_set_tiles(p, a3->B, a3->H, a3->W, HT_H);
     hipStream_t st = (hipStream_t)stream;
     const int cin = a3->c0 + a3->c1, nob = a3->cout / 16, nchunk = (cin + 15) / 16;
-    const int gx = p.ntiles < 512 ? (p.ntiles + 7) / 8 * 8 : 512;
-    // (fuse == 2: the chunk-outer kernel also where the chunk-inner one applies -- same-box A/B aid)
-#define SRBH_ENTRY_INNER(DS_, NC_)                                                                                                              \
-    do {                                                                                                                                       \
-        SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)hwgrad_entry_b16_kernel<DS_, NC_>, hipFuncAttributeMaxDynamicSharedMemorySize, WG16<3>::LDS_B2))); \
-        hipLaunchKernelGGL((hwgrad_entry_b16_kernel<DS_, NC_>), dim3(gx, nob), dim3(256), WG16<3>::LDS_B2, st, p);                                \
-    } while (0)
-    // (fuse == 3: without the whole-row 64-channel kernel -- A/B aid)
+    const int gx = wg_columns(p);
+    const dim3 grid(gx, nob);
+    int rc;
+    // (fuse == 2: the chunk-outer kernel also where the chunk-inner one applies; fuse == 3: without the whole-row 64-channel kernel -- same-box A/B aids)
     if ((fuse == 1) && a3->c0 == 64 && a3->c1 == 0 && ld0 == 64 && (a3->io & SRBH_WG_SRC0_H16) && !a3->pre_scale && !a3->pre_relu &&
         ((uintptr_t)a3->src0 & 15) == 0) {
-        if (ds16) {
-            SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)hwgrad_entry64_b16_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, WG64::LDS_B)));
-            hipLaunchKernelGGL((hwgrad_entry64_b16_kernel<1>), dim3(gx, nob), dim3(256), WG64::LDS_B, st, p);
-        } else {
-            SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)hwgrad_entry64_b16_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, WG64::LDS_B)));
-            hipLaunchKernelGGL((hwgrad_entry64_b16_kernel<0>), dim3(gx, nob), dim3(256), WG64::LDS_B, st, p);
-        }
+        if (ds16) rc = launch_wg<hwgrad_entry64_b16_kernel<1>>(grid, WG64::LDS_B, st, p);
+        else rc = launch_wg<hwgrad_entry64_b16_kernel<0>>(grid, WG64::LDS_B, st, p);
     } else if ((fuse == 1 || fuse == 3) && (nchunk == 2 || nchunk == 4)) {
-        if (ds16) { if (nchunk == 4) SRBH_ENTRY_INNER(1, 4); else SRBH_ENTRY_INNER(1, 2); }
-        else { if (nchunk == 4) SRBH_ENTRY_INNER(0, 4); else SRBH_ENTRY_INNER(0, 2); }
+        if (ds16 && nchunk == 4) rc = launch_wg<hwgrad_entry_b16_kernel<1, 4>>(grid, WG16<3>::LDS_B2, st, p);
+        else if (ds16) rc = launch_wg<hwgrad_entry_b16_kernel<1, 2>>(grid, WG16<3>::LDS_B2, st, p);
+        else if (nchunk == 4) rc = launch_wg<hwgrad_entry_b16_kernel<0, 4>>(grid, WG16<3>::LDS_B2, st, p);
+        else rc = launch_wg<hwgrad_entry_b16_kernel<0, 2>>(grid, WG16<3>::LDS_B2, st, p);
     } else if (ds16) {
-        SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)hwgrad_b16_kernel<3, 1, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, WG16<3>::LDS_B2)));
-        hipLaunchKernelGGL((hwgrad_b16_kernel<3, 1, 0, 1>), dim3(gx, nob), dim3(256), WG16<3>::LDS_B2, st, p);
+        rc = launch_wg<hwgrad_b16_kernel<3, 1, 0, 1>>(grid, WG16<3>::LDS_B2, st, p);
     } else {
-        SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)hwgrad_b16_kernel<3, 0, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, WG16<3>::LDS_B2)));
-        hipLaunchKernelGGL((hwgrad_b16_kernel<3, 0, 0, 1>), dim3(gx, nob), dim3(256), WG16<3>::LDS_B2, st, p);
+        rc = launch_wg<hwgrad_b16_kernel<3, 0, 0, 1>>(grid, WG16<3>::LDS_B2, st, p);
     }
-    SRBH_HIP(hipGetLastError());
+    if (rc) return rc;
     for (int k = 0; k < 2; ++k) {           // the two ordered reduces (3x3, then 1x1): as behind the separate calls
         const int taps = k == 0 ? 9 : 1;
         const srbh_hwgrad_args* a = k == 0 ? a3 : a1;
@@ -1514,20 +805,15 @@ extern "C" int srbh_act16_wgrad_b16(const void* x, int x_chunks_total, int cin, 
     SRBH_REQUIRE(cin > 0 && (cin & 15) == 0 && cin <= x_chunks_total * 32 && cout > 0 && (cout & 15) == 0 && cout <= 64 && (dy_ch0 & 15) == 0 &&
                  dy_ch0 + cout <= dy_chunks_total * 32, "srbh_act16_wgrad_b16: channel ranges (multiples of 16, inside the buffers)");
     WGParams p = {};
-    p.src0 = (const float*)x; p.src1 = nullptr; p.c0 = cin; p.c1 = 0; p.ld0 = 0; p.ld1 = 0;
-    p.dy = (const float*)dy; p.cout_total = cout; p.dw = dw; p.ws = ws; p.io = 0;
+    p.src0 = (const float*)x; p.c0 = cin;
+    p.dy = (const float*)dy; p.cout_total = cout; p.dw = dw; p.ws = ws;
     const Act16Geo gx_ = act16_geo(B, x_chunks_total, H, W), gd = act16_geo(B, dy_chunks_total, H, W);
     p.x_img_b = gx_.img_b; p.x_plane_b = gx_.plane_b; p.x_row_b = gx_.row_b;
     p.dy_img_b = gd.img_b; p.dy_plane_b = gd.plane_b; p.dy_row_b = gd.row_b; p.dy_ch0 = dy_ch0;
-    p.B = B; p.H = H; p.W = W;
-    p.tiles_x = (W + HT_W - 1) / HT_W;
-    p.tiles_per_img = p.tiles_x * ((H + HT_H - 1) / HT_H);
-    p.ntiles = p.tiles_per_img * B;
-    p.tiles_per_xcd = (p.ntiles + 7) / 8;
+    wg_set_tiles(p, B, H, W, HT_H);
     hipStream_t st = (hipStream_t)stream;
     const int nob = cout / 16;
-    int gx = p.ntiles < 512 ? (p.ntiles + 7) / 8 * 8 : 512;
-    SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)hwgrad_b16_kernel<3, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, WG16<3>::LDS_B)));
+    int gx = wg_columns(p);
     static const int zchunk_max = getenv("SRBH_WG_ZCHUNK_MAX") ? atoi(getenv("SRBH_WG_ZCHUNK_MAX")) : 256;
     p.zchunk = p.ntiles <= zchunk_max ? 1 : 0;
     if (p.zchunk) {
@@ -1540,24 +826,14 @@ extern "C" int srbh_act16_wgrad_b16(const void* x, int x_chunks_total, int cin, 
         cols = cols < 8 ? 8 : cols;
         if (cols < gx) gx = cols;
     }
-    hipLaunchKernelGGL((hwgrad_b16_kernel<3, 1, 1>), dim3(gx, nob, p.zchunk ? cin / 16 : 1), dim3(256), WG16<3>::LDS_B, st, p);
-    SRBH_HIP(hipGetLastError());
-    constexpr int SLICES = 16;
+    if (int rc = launch_wg<hwgrad_b16_kernel<3, 1, 1>>(dim3(gx, nob, p.zchunk ? cin / 16 : 1), WG16<3>::LDS_B, st, p)) return rc;
     const int taps = 9, nchunk = cin / 16;
     const long U = (long)nob * nchunk * taps * 256;
+    // few partial slots: the one-stage reduce; otherwise (and always under srbh_hwgrad_defer -- srbh_rrdbnet_trunk_train_backward batches a
+    // dense block's five) the two-stage ordered reduce
+    if (g_red_defer || gx > 128) return reduce_partials(ws, dw, U, gx, nchunk, taps, cout, cin, st);
     const int total = cout * cin * taps;
-    if (g_red_defer)          // (srbh_hwgrad_defer: the two-stage ordered reduce, queued -- srbh_rrdbnet_trunk_train_backward batches a dense block's five)
-        return reduce_partials(ws, dw, U, gx, nchunk, taps, cout, cin, st);
-    if (gx <= 128) {
-        hipLaunchKernelGGL(hwgrad_reduce_direct_kernel, dim3((total + 255) / 256), dim3(256), 0, st, ws, dw, U, gx, nchunk, taps, cout, cin);
-        SRBH_HIP(hipGetLastError());
-        return SRBH_OK;
-    }
-    float* tmp = ws + (long)WS_SLOTS * U;
-    const int per = (gx + SLICES - 1) / SLICES;
-    hipLaunchKernelGGL(hwgrad_reduce1_kernel, dim3((unsigned)((U + 255) / 256), SLICES), dim3(256), 0, st, ws, tmp, U, gx, per);
-    SRBH_HIP(hipGetLastError());
-    hipLaunchKernelGGL(hwgrad_reduce2_kernel, dim3((total + 255) / 256), dim3(256), 0, st, tmp, dw, U, SLICES, nchunk, taps, cout, cin);
+    hipLaunchKernelGGL(hwgrad_reduce_direct_kernel, dim3((total + 255) / 256), dim3(256), 0, st, ws, dw, U, gx, nchunk, taps, cout, cin);
     SRBH_HIP(hipGetLastError());
     return SRBH_OK;
 }

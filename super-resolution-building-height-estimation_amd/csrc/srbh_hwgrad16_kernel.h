@@ -1,5 +1,6 @@
 // srbh_hwgrad16_kernel.h -- weight gradient of the head's dominant layer (3x3, 16 -> 16 channels, one fp32 NHWC source, bf16 operands)
-// in the shape of hconv16_kernel (included by srbh_head_bwd.hip inside its anonymous namespace, after WGParams / bf16_pair).
+// in the shape of hconv16_kernel (included by srbh_head_bwd.hip inside its anonymous namespace, after srbh_hwgrad_b16_kernel.h: its tile
+// walk and its three-tap row product are that header's wg_walk / wg_tile / wg_row_taps).
 //
 // hwgrad_b16_kernel already walks tiles persistently, but one tile at a time: load -> LDS -> barrier -> MFMA with two workgroups per CU
 // to overlap (0.43 of the HBM peak; issuing the next tile's loads early cost 281 registers with its 8-row tiles).  Here the tile is
@@ -32,8 +33,8 @@ __global__ __launch_bounds__(256, 3) void hwgrad16_kernel(const WGParams p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, kk = lane >> 4;
     const int cg = tid & 3;
-    const int t_end = min((int)(blockIdx.x & 7) * p.tiles_per_xcd + p.tiles_per_xcd, p.ntiles);
-    const int t_first = (blockIdx.x & 7) * p.tiles_per_xcd + (blockIdx.x >> 3), t_step = gridDim.x >> 3;
+    int t_end;
+    const int t_first = wg_walk(p, t_end), t_step = wg_walk_step();
 
     floatx4 psc = {1.f, 1.f, 1.f, 1.f}, psh = {0.f, 0.f, 0.f, 0.f};
     if (p.pre_scale) { psc = *(const floatx4*)(p.pre_scale + cg * 4); psh = *(const floatx4*)(p.pre_shift + cg * 4); }
@@ -64,10 +65,8 @@ __global__ __launch_bounds__(256, 3) void hwgrad16_kernel(const WGParams p) {
     ldv_t ld[4];
     unsigned okx = 0;
     auto issue = [&](const int t) {
-        const int img = t / p.tiles_per_img;
-        const int trem = t - img * p.tiles_per_img;
-        const int ty = trem / p.tiles_x, tx = trem - ty * p.tiles_x;
-        const int Y0 = ty * 4, X0 = tx * 64;
+        int img, Y0, X0;
+        wg_tile<4>(p, t, img, Y0, X0);
         const char* xp = (const char*)p.src0 + (((long)img * p.H + (Y0 - 1)) * p.W + (X0 - 4)) * p.ld0 * (XS ? 2 : 4);
         const char* dp = (const char*)p.dy + (((long)img * p.H + Y0) * p.W + X0) * p.cout_total * (DS == 1 ? 2 : 4);
         okx = 0;
@@ -148,23 +147,13 @@ __global__ __launch_bounds__(256, 3) void hwgrad16_kernel(const WGParams p) {
         __syncthreads();           // stage `buf` complete; every wave is past the MFMAs of the tile before (other stage)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const uint2w a2 = *(const uint2w*)(stage + abase + g * 8);
-            const short4w a = __builtin_bit_cast(short4w, a2);
+            const short4w a = wg_frag(stage + abase + g * 8);
 #pragma unroll
-            for (int dy = 0; dy < 3; ++dy) {
-                const unsigned* rp = stage + bbase + dy * QX * 2 + g * 8;
-                const uint2w cur = *(const uint2w*)rp;
-                const unsigned pv = rp[-1], nx = rp[2];
-                const unsigned mid = __builtin_amdgcn_alignbit(cur[1], cur[0], 16);
-                const uint2w b0 = {__builtin_amdgcn_alignbit(cur[0], pv, 16), mid};
-                const uint2w b2 = {mid, __builtin_amdgcn_alignbit(nx, cur[1], 16)};
-                acc[dy * 3 + 0] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, __builtin_bit_cast(short4w, b0), acc[dy * 3 + 0], 0, 0, 0);
-                acc[dy * 3 + 1] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, __builtin_bit_cast(short4w, cur), acc[dy * 3 + 1], 0, 0, 0);
-                acc[dy * 3 + 2] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, __builtin_bit_cast(short4w, b2), acc[dy * 3 + 2], 0, 0, 0);
-            }
+            for (int dy = 0; dy < 3; ++dy) wg_row_taps(stage + bbase + dy * QX * 2 + g * 8, a, acc[dy * 3 + 0], acc[dy * 3 + 1], acc[dy * 3 + 2]);
         }
     }
-    // flush: D[row = oc = kk*4 + r][col = ci = l15]  (layout and workspace as hwgrad_b16_kernel: nob = nchunk = 1)
+    // flush: D[row = oc = kk*4 + r][col = ci = l15]  (layout and workspace as hwgrad_b16_kernel: nob = nchunk = 1; wg_flush's text, kept here:
+    // through the helper this kernel's instructions came out in another order)
     __syncthreads();
     float* s_red = wsm;
 #pragma unroll

@@ -266,12 +266,14 @@ def test_block_entry_fused_conv_pair_equals_the_two_convs(c0, c1, hw, stats):
 @pytest.mark.gpu
 @pytest.mark.parametrize("c0,c1,x16,g16,shape", [(64, 0, False, False, (2, 20, 72)), (64, 0, True, True, (2, 20, 72)), (16, 16, False, True, (2, 20, 72)),
                                                  (16, 16, False, False, (2, 20, 72)), (32, 0, False, True, (2, 20, 72)),
-                                                 (64, 0, True, False, (2, 20, 72)), (64, 0, True, True, (5, 250, 200)), (16, 16, False, True, (5, 250, 200))])
+                                                 (64, 0, True, False, (2, 20, 72)), (64, 0, True, True, (5, 250, 200)), (16, 16, False, True, (5, 250, 200)),
+                                                 (48, 0, False, False, (2, 20, 72)), (32, 16, False, True, (2, 20, 72))])
 def test_fused_entry_weight_gradients_equal_the_two_separate_calls(c0, c1, x16, g16, shape):
     """srbh_hconv_wgrad_entry_b16 (round 4): conv1's 3x3 and downsample[0]'s 1x1 weight gradients of a BasicBlock entry
     (SR/HRfuse.py:142-159) in ONE pass over the shared input -- the same bf16 products in the same order as the two separate
     srbh_hconv_wgrad_b16 calls: bit-identical results; ragged size included.  The chunk-inner kernel (2 / 4 chunks) and the whole-row
-    kernel of the 64-channel fp16 features (its register prefetch of the next tile: 640 tiles on 512 workgroups) are these calls' paths."""
+    kernel of the 64-channel fp16 features (its register prefetch of the next tile: 640 tiles on 512 workgroups) are these calls' paths;
+    three input chunks (48, 32 + 16) take the chunk-outer fused kernel."""
     from srbh_amd import hrfuse as H
     from srbh_amd import hrfuse_autograd as HA
     dev = "cuda:0"
@@ -429,6 +431,50 @@ def test_upsampler_weight_gradient_with_the_output_blocks_inside_the_walk(B, Hh,
     F.conv2d(xr, w0, padding=1).mul(gr).sum().backward()
     assert dw.shape == (64, 16, 3, 3)
     assert float((dw.double() - w0.grad).norm() / w0.grad.norm()) <= 1e-5
+
+
+def _upsampler_wgrad(B, Hh, Ww, g16, save_to=None):
+    """(the 16 -> 64 weight gradient of seeded, CPU-built inputs -- the same bits in every process --, the names of the hwgrad kernels that ran)"""
+    from torch.profiler import ProfilerActivity, profile
+    from srbh_amd import hrfuse as H
+    from srbh_amd import hrfuse_autograd as HA
+    g = torch.Generator().manual_seed(B + Ww)
+    nhwc = lambda t: t.to("cuda:0").contiguous(memory_format=torch.channels_last)        # noqa: E731
+    x = nhwc(torch.randn((B, 16, Hh, Ww), generator=g))
+    gy = nhwc(torch.randn((B, 64, Hh, Ww), generator=g) * 1e-2)
+    if g16:
+        gy = gy.bfloat16()
+    with H.head_precision("f16"), torch.no_grad(), profile(activities=[ProfilerActivity.CUDA]) as prof:
+        dw = HA.conv_wgrad([x], None, gy, 64, 3).cpu()
+    kernels = sorted({e.key for e in prof.key_averages() if "hwgrad" in e.key and "reduce" not in e.key})
+    if save_to:
+        torch.save({"dw": dw, "kernels": kernels}, save_to)
+    return dw, kernels
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("g16", [False, True])
+@pytest.mark.parametrize("B,Hh,Ww", [(2, 20, 72), (5, 250, 200)])
+def test_output_blocks_inside_the_walk_equal_the_grid_of_output_blocks(B, Hh, Ww, g16, tmp_path):
+    """hwgrad_ob_b16_kernel (the four dY blocks inside the tile walk) against hwgrad_b16_kernel with grid.y = 4 (SRBH_WGRAD_OB_INNER=0, read
+    once per process: a fresh child): same walk, products and flush, so the 16 -> 64 gradient is the same bits; a ragged shape and 640 tiles
+    on 512 workgroups, fp32 and bf16 dY.  Which kernel ran in which process is read from the profiler's kernel names: were the knob
+    ignored, the test would compare a kernel with itself."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = str(tmp_path / "dw.pt")
+    code = ("import sys; sys.path.insert(0, %r); from tests import test_gpu_head_f16 as T; T._upsampler_wgrad(%d, %d, %d, %r, %r)"
+            % (root, B, Hh, Ww, g16, out))
+    r = subprocess.run([sys.executable, "-c", code], cwd=root, env=dict(os.environ, SRBH_WGRAD_OB_INNER="0"), capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    dw, kernels = _upsampler_wgrad(B, Hh, Ww, g16)
+    ref = torch.load(out)
+    assert len(kernels) == 1 and "hwgrad_ob_b16_kernel" in kernels[0], kernels
+    assert len(ref["kernels"]) == 1 and "hwgrad_b16_kernel" in ref["kernels"][0], ref["kernels"]
+    assert dw.shape == (64, 16, 3, 3) and float(dw.abs().max()) > 0
+    assert torch.equal(dw, ref["dw"])
 
 
 def test_packs_refreshed_behind_the_optimizer_step_equal_the_lazy_packs():
