@@ -21,7 +21,7 @@
 // output rows -- 6 x 6 instead of 6 x 9 instructions; conv2 and the gathered edge unit have no such reuse and pair taps (0,1) (2,3) (4,5) (6,7)
 // (8,-): 5 instead of 9.  The sum over a pixel's 144 products is the same set of products in another order: the outputs equal the
 // two-launch chain's up to the last fp16 bit on a small fraction of the elements (tests/test_gpu_hblock16.py), no longer bit for bit.
-// The walk, the XCD-contiguous tile ranges and the two-tiles-ahead loads are hconv16_kernel's.
+// The walk (srbh_head_walk.h), the XCD-contiguous tile ranges and the two-tiles-ahead loads are hconv16_kernel's.
 // Restrictions (host: srbh_hblock16_supported): 16 channels, fp16 NHWC input, W % 64 == 0, H % 4 == 0.
 struct HBlkParams {
     const void* x;                  // fp16 [B][H][W][16]
@@ -45,8 +45,8 @@ __global__ __launch_bounds__(256, 2) void hblock16_kernel(const HBlkParams p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, kk = lane >> 4;
     const int cg = tid & 3;
-    const int t_end = min((int)(blockIdx.x & 7) * p.tiles_per_xcd + p.tiles_per_xcd, p.ntiles);
-    const int t_first = (blockIdx.x & 7) * p.tiles_per_xcd + (blockIdx.x >> 3), t_step = gridDim.x >> 3;
+    int t_first, t_end, t_step;
+    head_walk(p, t_first, t_end, t_step);
 
     // ---- per-thread constants
     // A operands: lane (oc = l15, kk) holds input channels 8 (kk & 1) .. + 7 of tap tA (kk < 2) / tB (kk >= 2, zero when the pair has no
@@ -124,9 +124,8 @@ __global__ __launch_bounds__(256, 2) void hblock16_kernel(const HBlkParams p) {
     unsigned okmask[2] = {0u, 0u};
     auto issue = [&](auto slot_tag, const int t) {
         constexpr int SL = decltype(slot_tag)::value;
-        const int img = t / p.tiles_per_img;
-        const int trem = t - img * p.tiles_per_img;
-        const int ty = trem / p.tiles_x, tx = trem - ty * p.tiles_x;
+        int img, ty, tx;
+        head_tile(p, t, img, ty, tx);
         const int Y0 = ty * 4, X0 = tx * 64;
         const long org = (((long)img * p.H + (Y0 - 2)) * p.W + (X0 - 2)) * 32;
         const char* tp = (const char*)p.x + org;
@@ -182,9 +181,8 @@ __global__ __launch_bounds__(256, 2) void hblock16_kernel(const HBlkParams p) {
     auto tile = [&](auto slot_tag, const int t, const int buf) {
         char* const sx = s_x + buf * XSTAGE_B;
         commit(slot_tag, sx);
-        const int img = t / p.tiles_per_img;
-        const int trem = t - img * p.tiles_per_img;
-        const int ty = trem / p.tiles_x, tx = trem - ty * p.tiles_x;
+        int img, ty, tx;
+        head_tile(p, t, img, ty, tx);
         const int Y0 = ty * 4, X0 = tx * 64;
         // (into the registers `commit` has just emptied; ALWAYS issued -- behind the range's end the tile is loaded again and never used -- so that
         //  the number of memory operations between a slot's loads and their use is a compile-time constant: see `issue`)

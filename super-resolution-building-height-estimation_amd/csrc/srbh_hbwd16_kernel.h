@@ -1,5 +1,6 @@
 // srbh_hbwd16_kernel.h -- the backward of one 3x3, 16 -> 16 convolution of a BasicBlock behind its BatchNorm, as ONE pass (round 5).
-// Included by srbh_head_bwd.hip inside its anonymous namespace (after WG16T / wg_row_taps / bf16_pair / widen_b4 / NSLOT).
+// Included by srbh_head_bwd.hip inside its anonymous namespace (after WG16T / wg_row_taps / bf16_pair / widen_b4 / NSLOT); the tile walk is
+// srbh_head_walk.h's.
 //
 // Reference graph (SR/HRfuse.py:142-159 through torch autograd): y = bn(conv(x')).  Given g = dL/dy, the three consumers of
 //      dc = coef * (g' - k1 - xhat * k2),   g' = g [masked by the ReLU behind the BatchNorm],  xhat = (c - mean) * invstd
@@ -65,8 +66,8 @@ __global__ __launch_bounds__(256, 2) void hbwd16_kernel(const HBParams p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, kk = lane >> 4;
     const int cg = tid & 3;
-    const int t_end = min((int)(blockIdx.x & 7) * p.tiles_per_xcd + p.tiles_per_xcd, p.ntiles);
-    const int t_first = (blockIdx.x & 7) * p.tiles_per_xcd + (blockIdx.x >> 3), t_step = gridDim.x >> 3;
+    int t_first, t_end, t_step;
+    head_walk(p, t_first, t_end, t_step);
 
     // ---- per-channel constants live in LDS (13 rows of 16 floats behind the two stages) and are read where they are used: as 52 registers
     // held over the walk they pushed the kernel 15-52 registers over the 256 of two waves per SIMD (scratch spills)
@@ -127,9 +128,8 @@ __global__ __launch_bounds__(256, 2) void hbwd16_kernel(const HBParams p) {
     floatx4 lc[NIX][4], lx[NIX][4];
     unsigned okx = 0;
     auto issue = [&](const int t) {
-        const int img = t / p.tiles_per_img;
-        const int trem = t - img * p.tiles_per_img;
-        const int ty = trem / p.tiles_x, tx = trem - ty * p.tiles_x;
+        int img, ty, tx;
+        head_tile(p, t, img, ty, tx);
         const int Y0 = ty * 4, X0 = tx * 64;
         const long org = (((long)img * p.H + (Y0 - 1)) * p.W + (X0 - 4)) * 16;
         const char* gp = (const char*)p.g + org * 2;
@@ -218,9 +218,8 @@ __global__ __launch_bounds__(256, 2) void hbwd16_kernel(const HBParams p) {
     for (int t = t_first; t < t_end; t += t_step, buf ^= 1) {
         unsigned* const stage = s_base + buf * G::STAGE_DW;
         commit(stage);
-        const int img = t / p.tiles_per_img;
-        const int trem = t - img * p.tiles_per_img;
-        const int ty = trem / p.tiles_x, tx = trem - ty * p.tiles_x;
+        int img, ty, tx;
+        head_tile(p, t, img, ty, tx);
         const long pix0 = ((long)img * p.H + ty * 4 + wave) * p.W + tx * 64 + l15;
         // epilogue operands of THIS tile first (c of the statistics / the skip gradient), then the next tile's window
         floatx4 rres[BS != 0 ? 4 : 1];

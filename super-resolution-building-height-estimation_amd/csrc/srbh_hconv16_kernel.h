@@ -6,7 +6,8 @@
 // kernel-argument load, input load, LDS, MFMA, residual load, store), not by bytes: it moves exactly the algorithmic 537 MB at
 // 3.4 TB/s, does not speed up when the bytes are halved, and a persistent walk bolted into the template blew its registers.  This
 // kernel is written around the walk:
-//   * a few workgroups per CU, each walks its XCD's contiguous run of tiles (halo rows from that XCD's L2);
+//   * a few workgroups per CU, each walks its XCD's contiguous run of tiles (halo rows from that XCD's L2; head_walk / head_tile of
+//     srbh_head_walk.h, as in every persistent head kernel);
 //   * the weights (9 taps x 8 bytes per lane) are loaded once per workgroup;
 //   * two LDS stages: while tile k is multiplied out of stage k&1 and stored, the global loads of tile k+1 are in flight (issued
 //     right after tile k went to LDS) and the residual of tile k was requested before its MFMAs -- one barrier per tile;
@@ -38,8 +39,8 @@ __global__ __launch_bounds__(256, 3) void hconv16_kernel(const HParams p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, kk = lane >> 4;
     const int cg = tid & 3;
-    const int t_end = min((int)(blockIdx.x & 7) * p.tiles_per_xcd + p.tiles_per_xcd, p.ntiles);
-    const int t_first = (blockIdx.x & 7) * p.tiles_per_xcd + (blockIdx.x >> 3), t_step = gridDim.x >> 3;
+    int t_first, t_end, t_step;
+    head_walk(p, t_first, t_end, t_step);
 
     // ---- per-thread constants of the walk
     short4v wa[9];
@@ -100,9 +101,8 @@ __global__ __launch_bounds__(256, 3) void hconv16_kernel(const HParams p) {
     constexpr bool res16 = (IO & 1) != 0, out16 = (IO & 2) != 0;
     auto issue = [&](auto slot_tag, const int t) {
         constexpr int SL = decltype(slot_tag)::value;
-        const int img = t / p.tiles_per_img;
-        const int trem = t - img * p.tiles_per_img;
-        const int ty = trem / p.tiles_x, tx = trem - ty * p.tiles_x;
+        int img, ty, tx;
+        head_tile(p, t, img, ty, tx);
         const int Y0 = ty * 4, X0 = tx * 64;
         const char* tp = (const char*)p.src0 + (((long)img * p.H + (Y0 - 1)) * p.W + (X0 - 1)) * p.ld0 * (S16 ? 2 : 4);
         okmask[SL] = 0;
@@ -164,9 +164,8 @@ __global__ __launch_bounds__(256, 3) void hconv16_kernel(const HParams p) {
     auto tile = [&](auto slot_tag, const int t, const int buf) {
         char* const stage = s_base + buf * STAGE_B;
         commit(slot_tag, stage);
-        const int img = t / p.tiles_per_img;
-        const int trem = t - img * p.tiles_per_img;
-        const int ty = trem / p.tiles_x, tx = trem - ty * p.tiles_x;
+        int img, ty, tx;
+        head_tile(p, t, img, ty, tx);
         const long pix0 = ((long)img * p.H + ty * 4 + wave) * p.W + tx * 64 + l15;
         // this tile's residual first, then the next tile's input: the epilogue can wait for the residual alone
         floatx4 rres[4];

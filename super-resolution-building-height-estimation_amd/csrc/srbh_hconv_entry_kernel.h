@@ -38,8 +38,8 @@ __global__ __launch_bounds__(256, SRBH_ENTRY_WGS_PER_CU) void hconv_entry_kernel
     const int l15 = lane & 15, kk = lane >> 4;
     const int cg = tid & 3;
     const int nchunk = e.nchunk;
-    const int t_end = min((int)(blockIdx.x & 7) * p.tiles_per_xcd + p.tiles_per_xcd, p.ntiles);
-    const int t_first = (blockIdx.x & 7) * p.tiles_per_xcd + (blockIdx.x >> 3), t_step = gridDim.x >> 3;
+    int t_first, t_end, t_step;
+    head_walk(p, t_first, t_end, t_step);
 
     for (int u = tid; u < nchunk * 10 * 64; u += 256) {
         const int c = u / 640, r = u - c * 640, tap = r >> 6, ln = r & 63;
@@ -79,9 +79,8 @@ __global__ __launch_bounds__(256, SRBH_ENTRY_WGS_PER_CU) void hconv_entry_kernel
     unsigned okmask = 0;
     const int usafe = p.W + 1;          // window pixel offset of the tile's pixel (Y0, X0): always inside the image
     auto issue = [&](const int t, const int c) {
-        const int img = t / p.tiles_per_img;
-        const int trem = t - img * p.tiles_per_img;
-        const int ty = trem / p.tiles_x, tx = trem - ty * p.tiles_x;
+        int img, ty, tx;
+        head_tile(p, t, img, ty, tx);
         const int Y0 = ty * 4, X0 = tx * 64;
         const bool in0 = c * 16 < p.c0;
         const int ldp = in0 ? p.ld0 : p.ld1;
@@ -156,9 +155,8 @@ __global__ __launch_bounds__(256, SRBH_ENTRY_WGS_PER_CU) void hconv_entry_kernel
                 }
             }
         }
-        const int img = t / p.tiles_per_img;
-        const int trem = t - img * p.tiles_per_img;
-        const int ty = trem / p.tiles_x, tx = trem - ty * p.tiles_x;
+        int img, ty, tx;
+        head_tile(p, t, img, ty, tx);
         const long pix0 = ((long)img * p.H + ty * 4 + wave) * p.W + tx * 64 + l15;
         float* const o1 = p.out + pix0 * p.out_ld + p.out_coff + kk * 4;
         float* const o2 = e.out2 + pix0 * e.out2_ld + e.out2_coff + kk * 4;
@@ -244,8 +242,8 @@ __global__ __launch_bounds__(256, 1) void hconv_entry64_kernel(const EParams e) 
     char* const s_w = s_base + 2 * STAGE_B;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, kk = lane >> 4;
-    const int t_end = min((int)(blockIdx.x & 7) * p.tiles_per_xcd + p.tiles_per_xcd, p.ntiles);
-    const int t_first = (blockIdx.x & 7) * p.tiles_per_xcd + (blockIdx.x >> 3), t_step = gridDim.x >> 3;
+    int t_first, t_end, t_step;
+    head_walk(p, t_first, t_end, t_step);
     for (int u = tid; u < NC * 10 * 64; u += 256) {
         const int c = u / 640, r = u - c * 640, tap = r >> 6, ln = r & 63;
         const short4v v = tap < 9 ? ((const short4v*)p.w)[(c * 9 + tap) * 64 + ln] : ((const short4v*)e.w2)[c * 64 + ln];
@@ -265,9 +263,8 @@ __global__ __launch_bounds__(256, 1) void hconv_entry64_kernel(const EParams e) 
     float ssum[4] = {0.f, 0.f, 0.f, 0.f}, ssq[4] = {0.f, 0.f, 0.f, 0.f}, dsum[4] = {0.f, 0.f, 0.f, 0.f}, dsq[4] = {0.f, 0.f, 0.f, 0.f};
     uint4e ld[NIT];
     auto issue = [&](const int t) {
-        const int img = t / p.tiles_per_img;
-        const int trem = t - img * p.tiles_per_img;
-        const int ty = trem / p.tiles_x, tx = trem - ty * p.tiles_x;
+        int img, ty, tx;
+        head_tile(p, t, img, ty, tx);
         const int Y0 = ty * 4, X0 = tx * 64;
         const short* tp = (const short*)p.src0 + (((long)img * p.H + (Y0 - 1)) * p.W + (X0 - 1)) * 64 + pc * 8;
 #pragma unroll
@@ -318,9 +315,8 @@ __global__ __launch_bounds__(256, 1) void hconv_entry64_kernel(const EParams e) 
                 }
             }
         }
-        const int img = t / p.tiles_per_img;
-        const int trem = t - img * p.tiles_per_img;
-        const int ty = trem / p.tiles_x, tx = trem - ty * p.tiles_x;
+        int img, ty, tx;
+        head_tile(p, t, img, ty, tx);
         const long pix0 = ((long)img * p.H + ty * 4 + wave) * p.W + tx * 64 + l15;
         float* const o1 = p.out + pix0 * p.out_ld + p.out_coff + kk * 4;
         float* const o2 = e.out2 + pix0 * e.out2_ld + e.out2_coff + kk * 4;

@@ -22,8 +22,8 @@ __global__ __launch_bounds__(256, 2) void hconv_up_kernel(const HParams p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, kk = lane >> 4;
     const int cg = tid & 3;
-    const int t_end = min((int)(blockIdx.x & 7) * p.tiles_per_xcd + p.tiles_per_xcd, p.ntiles);
-    const int t_first = (blockIdx.x & 7) * p.tiles_per_xcd + (blockIdx.x >> 3), t_step = gridDim.x >> 3;
+    int t_first, t_end, t_step;
+    head_walk(p, t_first, t_end, t_step);
     for (int u = tid; u < 36 * 64; u += 256) *(short4v*)(s_w + (long)u * 8) = ((const short4v*)p.w)[u];
     floatx4 e_bias[4];
 #pragma unroll
@@ -51,9 +51,8 @@ __global__ __launch_bounds__(256, 2) void hconv_up_kernel(const HParams p) {
     typedef typename std::conditional<S16 != 0, float2v, floatx4>::type ldv_t;
     ldv_t ld[NIT];
     auto issue = [&](const int t) {
-        const int img = t / p.tiles_per_img;
-        const int trem = t - img * p.tiles_per_img;
-        const int ty = trem / p.tiles_x, tx = trem - ty * p.tiles_x;
+        int img, ty, tx;
+        head_tile(p, t, img, ty, tx);
         const int Y0 = ty * 4, X0 = tx * 64;
         const char* tp = (const char*)p.src0 + (((long)img * p.H + (Y0 - 1)) * p.W + (X0 - 1)) * p.ld0 * (S16 ? 2 : 4);
 #pragma unroll
@@ -107,9 +106,8 @@ __global__ __launch_bounds__(256, 2) void hconv_up_kernel(const HParams p) {
                 for (int ob = 0; ob < 4; ++ob) acc[ob][i] = __builtin_amdgcn_mfma_f32_16x16x16f16(wa[ob], b, acc[ob][i], 0, 0, 0);
             }
         }
-        const int img = t / p.tiles_per_img;
-        const int trem = t - img * p.tiles_per_img;
-        const int ty = trem / p.tiles_x, tx = trem - ty * p.tiles_x;
+        int img, ty, tx;
+        head_tile(p, t, img, ty, tx);
         const int Y = ty * 4 + wave;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {

@@ -17,6 +17,7 @@
 //  * aggregate_kernel   : aggregate_torch (aggregate_utils.py:29-41).
 #include <stdlib.h>
 #include "srbh_internal.h"
+#include "srbh_head_walk.h"
 
 #include <type_traits>
 
@@ -128,9 +129,7 @@ __global__ __launch_bounds__(256) void hconv_f32_kernel(const HParams p) {
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, kk = lane >> 4;
-    // XCD-aware tile order: workgroups are dealt round-robin to the 8 XCDs (blockIdx % 8), each with its own L2.  Consecutive tiles
-    // (x-neighbours, then the next tile row) share halo rows -- 55 % more input rows than a tile owns at 4-row tiles -- so every
-    // XCD walks its own contiguous run of tiles and the halo re-reads hit that XCD's L2 instead of going out to the fabric.
+    // XCD-aware tile order (srbh_head_walk.h), ONE tile per workgroup.
     // (A PERSISTENT walk -- a few workgroups per CU looping over their XCD's tiles, BatchNorm statistics flushed once per workgroup,
     // optionally with the next tile's loads issued ahead of this tile's MFMAs -- was measured in round 2: the loop lets the compiler
     // keep ~80 more loop-invariant values in registers (182 VGPRs, occupancy 2: 180 us vs 160; pipelined 255 + 52 AGPRs, occupancy
@@ -138,9 +137,8 @@ __global__ __launch_bounds__(256) void hconv_f32_kernel(const HParams p) {
     // for a kernel written around it, not for this template.  DESIGN.md 5.0b / 8.)
     const int t = (blockIdx.x & 7) * p.tiles_per_xcd + (blockIdx.x >> 3);
     if (t >= p.ntiles) return;
-    const int img = t / p.tiles_per_img;
-    const int trem = t - img * p.tiles_per_img;
-    const int ty = trem / p.tiles_x, tx = trem - ty * p.tiles_x;
+    int img, ty, tx;
+    head_tile_v(p, t, img, ty, tx);
     const int Y0 = ty * HT_H, X0 = tx * HT_W;
     const int cin = p.c0 + p.c1;
     const int nchunk = (cin + HC - 1) / HC;
@@ -658,25 +656,27 @@ __global__ void nearest2x_kernel(const floatx4* __restrict__ src, floatx4* __res
 #include "srbh_hblock16_kernel.h"
 
 template <int NOB, int KS, int RPW, int OPT = 0>
-int launch_hconv(HParams& p, int B, int H, int W, hipStream_t st) {
+int launch_hconv(HParams& p, hipStream_t st) {
     constexpr bool H16 = OPT != 0;
     constexpr int LDS_T = H16 ? ((4 * RPW + 2) * (HT_W + 2) * 32 > 4 * 2 * NOB * 16 * 4 ? (4 * RPW + 2) * (HT_W + 2) * 32 : 4 * 2 * NOB * 16 * 4)
                               : (in_dw(RPW) + KS * KS * 4 * NOB * 64) * 4;
     constexpr int LDS_B = (NOB == 4 && LDS_T < PS2_STAGE_B) ? PS2_STAGE_B : LDS_T;     // (PixelShuffle store staging, see the epilogue)
-    p.tiles_x = (W + HT_W - 1) / HT_W;
-    p.tiles_per_img = p.tiles_x * ((H + 4 * RPW - 1) / (4 * RPW));
-    p.ntiles = p.tiles_per_img * B;
-    p.tiles_per_xcd = (p.ntiles + 7) / 8;
-    const int nblocks = p.tiles_per_xcd * 8;
+    head_set_tiles(p, p.B, p.H, p.W, 4 * RPW);
+    const dim3 grid(p.tiles_per_xcd * 8);              // one tile per workgroup
     static const int lds_floor = getenv("SRBH_HCONV_LDS") ? atoi(getenv("SRBH_HCONV_LDS")) : 0;     // developer aid: occupancy A/B
     const int lds_b = H16 && lds_floor > LDS_B ? lds_floor : LDS_B;
-    if (lds_b > 65536 || LDS_B > 65536) {
-        SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)hconv_f32_kernel<NOB, KS, RPW, OPT>,
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds_b > LDS_B ? lds_b : LDS_B)));
-    }
-    hipLaunchKernelGGL((hconv_f32_kernel<NOB, KS, RPW, OPT>), dim3(nblocks), dim3(256), lds_b, st, p);
-    SRBH_HIP(hipGetLastError());
-    return SRBH_OK;
+    if (lds_b > 65536) return launch<hconv_f32_kernel<NOB, KS, RPW, OPT>, true>(grid, lds_b, st, p);
+    return launch<hconv_f32_kernel<NOB, KS, RPW, OPT>>(grid, lds_b, st, p);
+}
+// the template's one ladder: (output blocks, kernel size) -> <NOB, KS>
+template <int RPW, int OPT>
+int hconv_template_form(HParams& p, int nob, int ksize, hipStream_t st) {
+    return with_const<3>(nob == 4 ? 2 : nob - 1, [&](auto n) {
+        return with_const<2>(ksize == 3, [&](auto k) {
+            constexpr int NOB = decltype(n)::value == 2 ? 4 : decltype(n)::value + 1, KS = decltype(k)::value ? 3 : 1;
+            return launch_hconv<NOB, KS, RPW, OPT>(p, st);
+        });
+    });
 }
 
 // tile height: 4-row tiles (RPW 1) by default; SRBH_HCONV_RPW=2 selects the 8-row tiles (A/B aid)
@@ -769,21 +769,15 @@ int hconv_entry_wgs_cap() { static const int v = getenv("SRBH_HCONV_ENTRY_WGS") 
 int hblock16_wgs_cap() { static const int v = getenv("SRBH_HBLOCK16_WGS") ? atoi(getenv("SRBH_HBLOCK16_WGS")) : 512; return v; }
 }  // namespace srbh
 
-static int hconv_impl(const srbh_hconv_args* a, void* stream, const int opt) {
-    const bool h16 = opt != 0;
-    SRBH_REQUIRE(a && a->src0 && a->w && a->out, "srbh_hconv_f32: null pointer");
-    SRBH_REQUIRE(a->c0 > 0 && a->c1 >= 0 && (a->c1 == 0 || a->src1), "srbh_hconv_f32: bad channel split %d+%d", a->c0, a->c1);
-    SRBH_REQUIRE(a->B > 0 && a->H > 0 && a->W > 0, "srbh_hconv_f32: bad geometry");
-    SRBH_REQUIRE(a->ksize == 3 || a->ksize == 1, "srbh_hconv_f32: ksize must be 1 or 3 (got %d)", a->ksize);
-    SRBH_REQUIRE(a->cout >= 1 && a->cout <= 64, "srbh_hconv_f32: cout must be in 1..64 (got %d)", a->cout);
-    SRBH_REQUIRE(!a->pixelshuffle2 || a->cout % 4 == 0, "srbh_hconv_f32: PixelShuffle(2) needs cout %% 4 == 0");
-    const int nob = (a->cout + 15) / 16;
-    SRBH_REQUIRE(nob == 1 || nob == 2 || nob == 4, "srbh_hconv_f32: cout must be <=32 or in 49..64 (got %d)", a->cout);
-    HParams p;
+// every HParams field a kernel reads, from the arguments of one conv; the tile geometry is set by the form that launches (head_set_tiles)
+static HParams hparams_of(const srbh_hconv_args* a) {
+    HParams p = {};
     p.src0 = a->src0; p.src1 = a->src1; p.c0 = a->c0; p.c1 = a->c1;
     p.pre_scale = a->pre_scale; p.pre_shift = a->pre_shift; p.pre_relu = a->pre_relu;
     p.w = a->w; p.bias = a->bias;
-    p.cout = nob * 16; p.cout_store = a->cout;
+    p.cout = (a->cout + 15) / 16 * 16; p.cout_store = a->cout;
+    p.B = a->B; p.H = a->H; p.W = a->W; p.ps2 = a->pixelshuffle2;
+    p.out = a->out; p.stats = a->stats;
     p.ld0 = a->src0_ld > 0 ? a->src0_ld : a->c0;
     p.ld1 = a->src1_ld > 0 ? a->src1_ld : a->c1;
     p.out_ld = a->out_ld > 0 ? a->out_ld : a->cout;
@@ -794,6 +788,17 @@ static int hconv_impl(const srbh_hconv_args* a, void* stream, const int opt) {
     p.post_scale = a->post_scale; p.post_shift = a->post_shift; p.post_relu = a->post_relu;
     p.io_h16 = a->io_h16;
     p.bstat_c = a->bstat_c; p.bstat_mean = a->bstat_mean; p.bstat_invstd = a->bstat_invstd; p.bstat_ms = a->bstat_ms; p.bstat_mh = a->bstat_mh;
+    return p;
+}
+
+// the argument errors that do not depend on the kernel form (p: hparams_of(a), for the strides in effect)
+static int hconv_validate(const srbh_hconv_args* a, const HParams& p, const int opt) {
+    SRBH_REQUIRE(a->c0 > 0 && a->c1 >= 0 && (a->c1 == 0 || a->src1), "srbh_hconv_f32: bad channel split %d+%d", a->c0, a->c1);
+    SRBH_REQUIRE(a->B > 0 && a->H > 0 && a->W > 0, "srbh_hconv_f32: bad geometry");
+    SRBH_REQUIRE(a->ksize == 3 || a->ksize == 1, "srbh_hconv_f32: ksize must be 1 or 3 (got %d)", a->ksize);
+    SRBH_REQUIRE(a->cout >= 1 && a->cout <= 64, "srbh_hconv_f32: cout must be in 1..64 (got %d)", a->cout);
+    SRBH_REQUIRE(!a->pixelshuffle2 || a->cout % 4 == 0, "srbh_hconv_f32: PixelShuffle(2) needs cout %% 4 == 0");
+    SRBH_REQUIRE(p.cout == 16 || p.cout == 32 || p.cout == 64, "srbh_hconv_f32: cout must be <=32 or in 49..64 (got %d)", a->cout);
     if (a->bstat_c)
         SRBH_REQUIRE(a->stats && a->bstat_mean && a->bstat_invstd && !a->res1 && a->cout == 16 && (a->bstat_ms == nullptr) == (a->bstat_mh == nullptr) &&
                      ((uintptr_t)a->bstat_c & 15) == 0, "srbh_hconv: backward-statistics epilogue needs stats, mean, invstd, no residual, cout == 16");
@@ -811,108 +816,95 @@ static int hconv_impl(const srbh_hconv_args* a, void* stream, const int opt) {
     SRBH_REQUIRE(!a->pixelshuffle2 || (a->out_ld <= 0 && a->out_coff == 0), "srbh_hconv_f32: PixelShuffle store needs a dense output");
     SRBH_REQUIRE(!a->res1 || (a->cout % 4 == 0 && a->res1_ld % 4 == 0), "srbh_hconv_f32: residual epilogue needs 4-aligned channels");
     SRBH_REQUIRE(!a->res2 || a->res1, "srbh_hconv_f32: res2 requires res1");
-    p.B = a->B; p.H = a->H; p.W = a->W; p.ps2 = a->pixelshuffle2;
-    p.out = a->out; p.stats = a->stats;
-    hipStream_t st = (hipStream_t)stream;
-    if (a->stats && !a->stats_clean) { if (int rc = zero_async(a->stats, srbh_bn_stats_bytes(p.cout), st)) return rc; }
-    const int B = a->B, H = a->H, W = a->W;
-    // 16-bit operand forms: 4-row tiles (12.7 KiB staged tile; measured level with the 8-row form on single-chunk convs and
-    // 10-25 % ahead on the multi-chunk ones)
-#define SRBH_H16_DISPATCH(OPT_)                                                                                             \
-    do {                                                                                                                    \
-        if (a->ksize == 3)                                                                                                  \
-            return nob == 1 ? launch_hconv<1, 3, 1, OPT_>(p, B, H, W, st)                                                   \
-                            : (nob == 2 ? launch_hconv<2, 3, 1, OPT_>(p, B, H, W, st) : launch_hconv<4, 3, 1, OPT_>(p, B, H, W, st)); \
-        return nob == 1 ? launch_hconv<1, 1, 1, OPT_>(p, B, H, W, st)                                                       \
-                        : (nob == 2 ? launch_hconv<2, 1, 1, OPT_>(p, B, H, W, st) : launch_hconv<4, 1, 1, OPT_>(p, B, H, W, st)); \
-    } while (0)
-    if (a->pixelshuffle2 == 2) {      // the Upsampler conv with sub-pixel-major weight rows: its own persistent kernel (srbh_hconv_up_kernel.h)
-        const bool s16 = (a->io_h16 & SRBH_IO_SRC0_H16) != 0, o16u = (a->io_h16 & SRBH_IO_OUT_H16) != 0;
-        SRBH_REQUIRE(opt == 1 && a->ksize == 3 && a->c0 == 16 && a->c1 == 0 && a->cout == 64 && !a->pre_scale && !a->pre_relu && !a->res1 && !a->res2 &&
-                     !a->stats && !a->post_scale && !a->post_relu && !a->post_lrelu && !a->bstat_c && srbh_hconv_up_supported(H, W) && (p.ld0 & 3) == 0 &&
-                     ((uintptr_t)a->src0 & (s16 ? 7 : 15)) == 0 && ((uintptr_t)a->out & (o16u ? 7 : 15)) == 0 && (a->io_h16 & ~(SRBH_IO_SRC0_H16 | SRBH_IO_OUT_H16)) == 0,
-                     "srbh_hconv_h16: pixelshuffle2 == 2 (sub-pixel-major pack) is the fp16 16 -> 64 3x3 form without pre / post ops, W %% 64 == 0, H %% 4 == 0");
-        const int up_wgs = hconv_up_wgs_cap();
-        p.tiles_x = W / 64;
-        p.tiles_per_img = p.tiles_x * (H / 4);
-        p.ntiles = p.tiles_per_img * B;
-        p.tiles_per_xcd = (p.ntiles + 7) / 8;
-        const int per_xcd = p.tiles_per_xcd < up_wgs / 8 ? p.tiles_per_xcd : up_wgs / 8;
-        constexpr int LDSUP = 2 * 6 * 66 * 32 + 36 * 64 * 8;
-        if (s16 && o16u) hipLaunchKernelGGL((hconv_up_kernel<1, 1>), dim3(per_xcd * 8), dim3(256), LDSUP, st, p);
-        else if (s16) hipLaunchKernelGGL((hconv_up_kernel<1, 0>), dim3(per_xcd * 8), dim3(256), LDSUP, st, p);
-        else if (o16u) hipLaunchKernelGGL((hconv_up_kernel<0, 1>), dim3(per_xcd * 8), dim3(256), LDSUP, st, p);
-        else hipLaunchKernelGGL((hconv_up_kernel<0, 0>), dim3(per_xcd * 8), dim3(256), LDSUP, st, p);
-        SRBH_HIP(hipGetLastError());
-        count_path(PATH_HCONV_UP);
-        return SRBH_OK;
+    return SRBH_OK;
+}
+
+// which of a call's tensors hold 16-bit elements
+struct HIo { bool src16, out16, res16; };
+static HIo hio_of(const srbh_hconv_args* a) { return {(a->io_h16 & SRBH_IO_SRC0_H16) != 0, (a->io_h16 & SRBH_IO_OUT_H16) != 0, (a->io_h16 & SRBH_IO_RES1_H16) != 0}; }
+
+// ---- form 1: the Upsampler conv with sub-pixel-major weight rows (pixelshuffle2 == 2): hconv_up_kernel<S16, O16> (srbh_hconv_up_kernel.h)
+static int hconv_up_form(const srbh_hconv_args* a, HParams& p, const int opt, hipStream_t st) {
+    const HIo io = hio_of(a);
+    SRBH_REQUIRE(opt == 1 && a->ksize == 3 && a->c0 == 16 && a->c1 == 0 && a->cout == 64 && !a->pre_scale && !a->pre_relu && !a->res1 && !a->res2 &&
+                 !a->stats && !a->post_scale && !a->post_relu && !a->post_lrelu && !a->bstat_c && srbh_hconv_up_supported(a->H, a->W) && (p.ld0 & 3) == 0 &&
+                 ((uintptr_t)a->src0 & (io.src16 ? 7 : 15)) == 0 && ((uintptr_t)a->out & (io.out16 ? 7 : 15)) == 0 && (a->io_h16 & ~(SRBH_IO_SRC0_H16 | SRBH_IO_OUT_H16)) == 0,
+                 "srbh_hconv_h16: pixelshuffle2 == 2 (sub-pixel-major pack) is the fp16 16 -> 64 3x3 form without pre / post ops, W %% 64 == 0, H %% 4 == 0");
+    head_set_tiles(p, a->B, a->H, a->W, 4);
+    const int grid = head_walk_grid(p, hconv_up_wgs_cap());
+    if (grid <= 0) return hip_fail(hipErrorInvalidConfiguration, "hconv_up_kernel: SRBH_HCONV_UP_WGS below 8 leaves no workgroup");   // cap < 8: an error, nothing launched
+    constexpr int LDSUP = 2 * 6 * 66 * 32 + 36 * 64 * 8;
+    const int rc = with_const<2>(io.src16, [&](auto s) {
+        return with_const<2>(io.out16, [&](auto o) { return launch<hconv_up_kernel<decltype(s)::value, decltype(o)::value>>(dim3(grid), LDSUP, st, p); });
+    });
+    if (rc) return rc;
+    count_path(PATH_HCONV_UP);
+    return SRBH_OK;
+}
+
+// ---- form 2: the dominant layer shape on its own persistent, double-buffered kernel (srbh_hconv16_kernel.h)
+// 0: another form takes the call; 1: taken; 2: taken with a NARROW INPUT (the data gradients of the 1- / 7-channel output convs: fp32 source of
+// < 16 channels, any pixel stride)
+static int hconv16_takes(const srbh_hconv_args* a, const HParams& p, const int opt) {
+    const HIo io = hio_of(a);
+    const bool full16 = a->cout == 16 && (p.out_ld & 3) == 0 && (p.out_coff & 3) == 0 && ((uintptr_t)a->out & (io.out16 ? 7 : 15)) == 0;
+    const bool narrow = a->cout < 16 && !a->stats && !a->res1 && !io.out16;         // conv_last (1 / 7 channels): scalar stores
+    const bool nin = a->c0 < 16 && a->c1 == 0 && !io.src16 && !a->pre_scale && !a->pre_relu && !a->bstat_c && full16 && ((uintptr_t)a->src0 & 3) == 0;
+    // (a cap below 8 -- SRBH_HCONV16_WGS=0 -- sends every shape to the template)
+    const bool take = opt != 0 && hconv16_wgs_cap() >= 8 && a->ksize == 3 && (full16 || narrow) && (a->c0 == 16 || nin) && a->c1 == 0 && (a->W & 63) == 0 &&
+                      (a->H & 3) == 0 && !a->pixelshuffle2 && !a->res2 && !a->post_lrelu && (nin || (p.ld0 & 3) == 0) && (!a->res1 || (a->res1_ld & 3) == 0) &&
+                      (nin || ((uintptr_t)a->src0 & (io.src16 ? 7 : 15)) == 0) && ((uintptr_t)a->res1 & (io.res16 ? 7 : 15)) == 0;
+    return take ? (nin ? 2 : 1) : 0;
+}
+// hconv16_kernel<OPT, S16, IO, BS, NIN>: OPT = operand type, S16 = 16-bit source, IO = bit 0 a 16-bit residual that exists, bit 1 a 16-bit output
+static int hconv16_form(const srbh_hconv_args* a, HParams& p, const int opt, const bool nin, hipStream_t st) {
+    const HIo io = hio_of(a);
+    count_path(PATH_HCONV16);
+    head_set_tiles(p, a->B, a->H, a->W, 4);
+    const dim3 grid(head_walk_grid(p, hconv16_wgs_cap()));
+    constexpr int LDS16 = 2 * 6 * 66 * 32;
+    const int io_bits = (io.res16 && a->res1 ? 1 : 0) | (io.out16 ? 2 : 0);
+    if (a->bstat_c) {       // backward-statistics epilogues: the bf16-operand (data gradient) forms only; c rides in the residual's registers
+        SRBH_REQUIRE(opt == 2, "srbh_hconv_h16: the backward-statistics epilogue belongs to the bf16 data-gradient form");
+        return with_const<2>(io.src16, [&](auto s) {
+            return with_const<2>(io.out16, [&](auto o) { return launch<hconv16_kernel<2, decltype(s)::value, decltype(o)::value * 2, 1>>(grid, LDS16, st, p); });
+        });
     }
-    // the dominant layer shape has its own persistent, double-buffered kernel (srbh_hconv16_kernel.h)
-    const int k16_wgs = hconv16_wgs_cap();     // 0 = always the template
-    const bool src16 = (a->io_h16 & SRBH_IO_SRC0_H16) != 0, o16 = (a->io_h16 & SRBH_IO_OUT_H16) != 0, r16 = (a->io_h16 & SRBH_IO_RES1_H16) != 0;
-    const bool full16 = a->cout == 16 && (p.out_ld & 3) == 0 && (p.out_coff & 3) == 0 && ((uintptr_t)a->out & (o16 ? 7 : 15)) == 0;
-    const bool narrow = a->cout < 16 && !a->stats && !a->res1 && !o16;         // conv_last (1 / 7 channels): scalar stores
-    // narrow INPUT (the data gradients of the 1- / 7-channel output convs): fp32 source of < 16 channels, any pixel stride
-    const bool nin = a->c0 < 16 && a->c1 == 0 && !src16 && !a->pre_scale && !a->pre_relu && !a->bstat_c && full16 && ((uintptr_t)a->src0 & 3) == 0;
-    if (opt != 0 && k16_wgs >= 8 && a->ksize == 3 && (full16 || narrow) && (a->c0 == 16 || nin) && a->c1 == 0 && (W & 63) == 0 && (H & 3) == 0 &&
-        !a->pixelshuffle2 && !a->res2 && !a->post_lrelu && (nin || (p.ld0 & 3) == 0) &&
-        (!a->res1 || (a->res1_ld & 3) == 0) && (nin || ((uintptr_t)a->src0 & (src16 ? 7 : 15)) == 0) && ((uintptr_t)a->res1 & (r16 ? 7 : 15)) == 0) {
-        count_path(PATH_HCONV16);
-        p.tiles_x = W / 64;
-        p.tiles_per_img = p.tiles_x * (H / 4);
-        p.ntiles = p.tiles_per_img * B;
-        p.tiles_per_xcd = (p.ntiles + 7) / 8;
-        const int per_xcd = p.tiles_per_xcd < k16_wgs / 8 ? p.tiles_per_xcd : k16_wgs / 8;
-        constexpr int LDS16 = 2 * 6 * 66 * 32;
-        const int io = (r16 && a->res1 ? 1 : 0) | (o16 ? 2 : 0);
-#define SRBH_K16(O_, S_, I_) hipLaunchKernelGGL((hconv16_kernel<O_, S_, I_>), dim3(per_xcd * 8), dim3(256), LDS16, st, p)
-#define SRBH_K16_IO(O_, S_) do { switch (io) { case 0: SRBH_K16(O_, S_, 0); break; case 1: SRBH_K16(O_, S_, 1); break; \
-                                               case 2: SRBH_K16(O_, S_, 2); break; default: SRBH_K16(O_, S_, 3); } } while (0)
-        if (a->bstat_c) {       // backward-statistics epilogues: the bf16-operand (data gradient) forms only
-            SRBH_REQUIRE(opt == 2, "srbh_hconv_h16: the backward-statistics epilogue belongs to the bf16 data-gradient form");
-#define SRBH_K16_BS(S_, I_) hipLaunchKernelGGL((hconv16_kernel<2, S_, I_, 1>), dim3(per_xcd * 8), dim3(256), LDS16, st, p)
-            if (src16 && o16) SRBH_K16_BS(1, 2);
-            else if (src16) SRBH_K16_BS(1, 0);
-            else if (o16) SRBH_K16_BS(0, 2);
-            else SRBH_K16_BS(0, 0);
-#undef SRBH_K16_BS
-            SRBH_HIP(hipGetLastError());
-            return SRBH_OK;
-        }
-        if (nin) {
-#define SRBH_K16_NIN(O_, I_) hipLaunchKernelGGL((hconv16_kernel<O_, 0, I_, 0, 1>), dim3(per_xcd * 8), dim3(256), LDS16, st, p)
-            if (opt == 1) { switch (io) { case 0: SRBH_K16_NIN(1, 0); break; case 1: SRBH_K16_NIN(1, 1); break; case 2: SRBH_K16_NIN(1, 2); break; default: SRBH_K16_NIN(1, 3); } }
-            else { switch (io) { case 0: SRBH_K16_NIN(2, 0); break; case 1: SRBH_K16_NIN(2, 1); break; case 2: SRBH_K16_NIN(2, 2); break; default: SRBH_K16_NIN(2, 3); } }
-#undef SRBH_K16_NIN
-        } else
-        if (opt == 1 && !src16) SRBH_K16_IO(1, 0);
-        else if (opt == 1) SRBH_K16_IO(1, 1);
-        else if (!src16) SRBH_K16_IO(2, 0);
-        else SRBH_K16_IO(2, 1);
-#undef SRBH_K16_IO
-#undef SRBH_K16
-        SRBH_HIP(hipGetLastError());
-        return SRBH_OK;
-    }
+    return with_const<2>(opt - 1, [&](auto o) {
+        constexpr int OPT = decltype(o)::value + 1;
+        return with_const<4>(io_bits, [&](auto i) {
+            constexpr int IO = decltype(i)::value;
+            if (nin) return launch<hconv16_kernel<OPT, 0, IO, 0, 1>>(grid, LDS16, st, p);
+            return with_const<2>(io.src16, [&](auto s) { return launch<hconv16_kernel<OPT, decltype(s)::value, IO>>(grid, LDS16, st, p); });
+        });
+    });
+}
+
+// ---- form 3: the general template, one tile per workgroup (hconv_f32_kernel<NOB, KS, RPW, OPT>)
+static int hconv_template(const srbh_hconv_args* a, HParams& p, const int opt, hipStream_t st) {
     count_path(PATH_HCONV_TEMPLATE);
     SRBH_REQUIRE(!a->bstat_c, "srbh_hconv: the backward-statistics epilogue exists in the persistent 16 -> 16 3x3 kernel only (16-bit operand modes, W %% 64 == 0, H %% 4 == 0)");
     // (the template stages a 16-bit source as it is: no transform on the way)
-    SRBH_REQUIRE(!src16 || (!a->pre_scale && !a->pre_relu), "srbh_hconv_h16: a 16-bit src0 takes a pre-affine / ReLU only in the 16 -> 16 3x3 form");
-    if (opt == 1) SRBH_H16_DISPATCH(1);
-    if (opt == 2) SRBH_H16_DISPATCH(2);
-#undef SRBH_H16_DISPATCH
-    if (hconv_rpw_small() == 1) {
-        if (a->ksize == 3)
-            return nob == 1 ? launch_hconv<1, 3, 1>(p, B, H, W, st)
-                            : (nob == 2 ? launch_hconv<2, 3, 1>(p, B, H, W, st) : launch_hconv<4, 3, 1>(p, B, H, W, st));
-        return nob == 1 ? launch_hconv<1, 1, 1>(p, B, H, W, st)
-                        : (nob == 2 ? launch_hconv<2, 1, 1>(p, B, H, W, st) : launch_hconv<4, 1, 1>(p, B, H, W, st));
-    }
-    if (a->ksize == 3)
-        return nob == 1 ? launch_hconv<1, 3, 2>(p, B, H, W, st)
-                        : (nob == 2 ? launch_hconv<2, 3, 2>(p, B, H, W, st) : launch_hconv<4, 3, 2>(p, B, H, W, st));
-    return nob == 1 ? launch_hconv<1, 1, 2>(p, B, H, W, st)
-                    : (nob == 2 ? launch_hconv<2, 1, 2>(p, B, H, W, st) : launch_hconv<4, 1, 2>(p, B, H, W, st));
+    SRBH_REQUIRE(!hio_of(a).src16 || (!a->pre_scale && !a->pre_relu), "srbh_hconv_h16: a 16-bit src0 takes a pre-affine / ReLU only in the 16 -> 16 3x3 form");
+    const int nob = p.cout / 16;
+    // 16-bit operand forms: 4-row tiles (12.7 KiB staged tile; measured level with the 8-row form on single-chunk convs and
+    // 10-25 % ahead on the multi-chunk ones); fp32: hconv_rpw_small()
+    if (opt == 1) return hconv_template_form<1, 1>(p, nob, a->ksize, st);
+    if (opt == 2) return hconv_template_form<1, 2>(p, nob, a->ksize, st);
+    if (hconv_rpw_small() == 1) return hconv_template_form<1, 0>(p, nob, a->ksize, st);
+    return hconv_template_form<2, 0>(p, nob, a->ksize, st);
+}
+
+// validate, fill, choose the form, launch
+static int hconv_impl(const srbh_hconv_args* a, void* stream, const int opt) {
+    SRBH_REQUIRE(a && a->src0 && a->w && a->out, "srbh_hconv_f32: null pointer");
+    HParams p = hparams_of(a);
+    if (int rc = hconv_validate(a, p, opt)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (a->stats && !a->stats_clean) { if (int rc = zero_async(a->stats, srbh_bn_stats_bytes(p.cout), st)) return rc; }
+    if (a->pixelshuffle2 == 2) return hconv_up_form(a, p, opt, st);
+    if (const int k16 = hconv16_takes(a, p, opt)) return hconv16_form(a, p, opt, k16 == 2, st);
+    return hconv_template(a, p, opt, st);
 }
 
 extern "C" int srbh_hconv_f32(const srbh_hconv_args* a, void* stream) { return hconv_impl(a, stream, 0); }
@@ -922,7 +914,7 @@ extern "C" int srbh_hconv_h16(const srbh_hconv_args* a, int bf16, void* stream) 
 // (srbh_hconv_entry_kernel.h), otherwise the two template launches -- the results are the same either way.
 extern "C" int srbh_hconv_entry_h16(const srbh_hconv_args* c1, const srbh_hconv_args* ds, int bf16, void* stream) {
     SRBH_REQUIRE(c1 && ds, "srbh_hconv_entry_h16: null arguments");
-    const int wgs = hconv_entry_wgs_cap();      // 0 = never fuse
+    const int wgs = hconv_entry_wgs_cap();      // below 8 (0): never fuse
     const int cin = c1->c0 + c1->c1;
     const int ld0 = c1->src0_ld > 0 ? c1->src0_ld : c1->c0, ld1 = c1->src1_ld > 0 ? c1->src1_ld : c1->c1;
     const int dld0 = ds->src0_ld > 0 ? ds->src0_ld : ds->c0, dld1 = ds->src1_ld > 0 ? ds->src1_ld : ds->c1;
@@ -952,19 +944,14 @@ extern "C" int srbh_hconv_entry_h16(const srbh_hconv_args* c1, const srbh_hconv_
     hipStream_t st = (hipStream_t)stream;
     EParams e;
     HParams& p = e.a;
-    p.src0 = c1->src0; p.src1 = c1->src1; p.c0 = c1->c0; p.c1 = c1->c1;
+    p = hparams_of(c1);
+    // what the fused kernel must not see (`plain` has excluded every one of them; pointers that came along unused are dropped)
     p.pre_scale = nullptr; p.pre_shift = nullptr; p.pre_relu = 0;
-    p.w = c1->w; p.bias = c1->bias; p.cout = 16; p.cout_store = 16;
-    p.B = c1->B; p.H = c1->H; p.W = c1->W; p.ps2 = 0;
-    p.out = c1->out; p.stats = c1->stats;
-    p.ld0 = ld0; p.ld1 = ld1; p.out_ld = out1_ld; p.out_coff = c1->out_coff;
-    p.post_lrelu = 0; p.res1 = nullptr; p.res1_ld = 0; p.res1_scale = 1.f; p.res2 = nullptr; p.res2_ld = 0; p.res2_scale = 1.f;
-    p.post_scale = c1->post_scale; p.post_shift = c1->post_shift; p.post_relu = c1->post_relu; p.io_h16 = c1->io_h16 & SRBH_IO_OUT_H16;
+    p.ps2 = 0; p.post_lrelu = 0;
+    p.res1 = nullptr; p.res1_ld = 0; p.res1_scale = 1.f; p.res2 = nullptr; p.res2_ld = 0; p.res2_scale = 1.f;
+    p.io_h16 = c1->io_h16 & SRBH_IO_OUT_H16;
     p.bstat_c = p.bstat_mean = p.bstat_invstd = p.bstat_ms = p.bstat_mh = nullptr;
-    p.tiles_x = c1->W / 64;
-    p.tiles_per_img = p.tiles_x * (c1->H / 4);
-    p.ntiles = p.tiles_per_img * c1->B;
-    p.tiles_per_xcd = (p.ntiles + 7) / 8;
+    head_set_tiles(p, c1->B, c1->H, c1->W, 4);
     e.w2 = ds->w; e.bias2 = ds->bias; e.post2_scale = ds->post_scale; e.post2_shift = ds->post_shift;
     e.out2 = ds->out; e.out2_ld = out2_ld; e.out2_coff = ds->out_coff; e.stats2 = ds->stats;
     e.nchunk = cin / 16;
@@ -972,32 +959,21 @@ extern "C" int srbh_hconv_entry_h16(const srbh_hconv_args* c1, const srbh_hconv_
         if (!c1->stats_clean) { if (int rc = zero_async(c1->stats, srbh_bn_stats_bytes(16), st)) return rc; }
         if (!ds->stats_clean) { if (int rc = zero_async(ds->stats, srbh_bn_stats_bytes(16), st)) return rc; }
     }
-    const int per_xcd = p.tiles_per_xcd < wgs / 8 ? p.tiles_per_xcd : wgs / 8;
-    const int lds_b = 2 * 6 * 66 * 32 + e.nchunk * 640 * 8;
     const bool eo16 = (c1->io_h16 & SRBH_IO_OUT_H16) != 0;
     static const int e64 = getenv("SRBH_HCONV_ENTRY64") ? atoi(getenv("SRBH_HCONV_ENTRY64")) : 1;     // 0: the chunked kernel (A/B aid)
     if (e64 && es16 && !bf16 && c1->c0 == 64 && c1->c1 == 0 && ld0 == 64 && ((uintptr_t)c1->src0 & 15) == 0) {
-        // HRfeature's entry on whole 128-byte pixel rows, one workgroup per CU (srbh_hconv_entry_kernel.h)
+        // HRfeature's entry on whole 128-byte pixel rows, one workgroup per CU (srbh_hconv_entry_kernel.h): hconv_entry64_kernel<O16>
         constexpr int LDS64 = 2 * 4 * 6 * 66 * 32 + 4 * 640 * 8;
-        const int px64 = p.tiles_per_xcd < 32 ? p.tiles_per_xcd : 32;
-        if (eo16) {
-            SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)hconv_entry64_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS64)));
-            hipLaunchKernelGGL((hconv_entry64_kernel<1>), dim3(px64 * 8), dim3(256), LDS64, st, e);
-        } else {
-            SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)hconv_entry64_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS64)));
-            hipLaunchKernelGGL((hconv_entry64_kernel<0>), dim3(px64 * 8), dim3(256), LDS64, st, e);
-        }
-        SRBH_HIP(hipGetLastError());
-        return SRBH_OK;
+        const dim3 grid(head_walk_grid(p, 256));
+        return with_const<2>(eo16, [&](auto o) { return launch<hconv_entry64_kernel<decltype(o)::value>, true>(grid, LDS64, st, e); });
     }
-    if (es16 && eo16) hipLaunchKernelGGL((hconv_entry_kernel<1, 1, 1>), dim3(per_xcd * 8), dim3(256), lds_b, st, e);
-    else if (es16) hipLaunchKernelGGL((hconv_entry_kernel<1, 0, 1>), dim3(per_xcd * 8), dim3(256), lds_b, st, e);
-    else if (bf16 && eo16) hipLaunchKernelGGL((hconv_entry_kernel<2, 1>), dim3(per_xcd * 8), dim3(256), lds_b, st, e);
-    else if (bf16) hipLaunchKernelGGL((hconv_entry_kernel<2, 0>), dim3(per_xcd * 8), dim3(256), lds_b, st, e);
-    else if (eo16) hipLaunchKernelGGL((hconv_entry_kernel<1, 1>), dim3(per_xcd * 8), dim3(256), lds_b, st, e);
-    else hipLaunchKernelGGL((hconv_entry_kernel<1, 0>), dim3(per_xcd * 8), dim3(256), lds_b, st, e);
-    SRBH_HIP(hipGetLastError());
-    return SRBH_OK;
+    // hconv_entry_kernel<OPT, O16, S16>: fp16 sources (fp16 operands only) / bf16 operands / fp16 operands
+    const dim3 grid(head_walk_grid(p, wgs));
+    const int lds_b = 2 * 6 * 66 * 32 + e.nchunk * 640 * 8;
+    return with_const<3>(es16 ? 2 : bf16 ? 1 : 0, [&](auto v) {
+        constexpr int OPT = decltype(v)::value == 1 ? 2 : 1, S16 = decltype(v)::value == 2;
+        return with_const<2>(eo16, [&](auto o) { return launch<hconv_entry_kernel<OPT, decltype(o)::value, S16>>(grid, lds_b, st, e); });
+    });
 }
 
 extern "C" int srbh_hblock16_supported(int H, int W) { return H > 0 && W > 0 && (W & 63) == 0 && (H & 3) == 0; }
@@ -1011,19 +987,11 @@ extern "C" int srbh_hblock16_eval(const srbh_hblock16_args* a, void* stream) {
     const int wgs = hblock16_wgs_cap();      // two per CU
     HBlkParams p;
     p.x = a->x; p.w1 = a->w1; p.w2 = a->w2; p.s1 = a->scale1; p.h1 = a->shift1; p.s2 = a->scale2; p.h2 = a->shift2; p.out = a->out;
-    p.B = a->B; p.H = a->H; p.W = a->W;
-    p.tiles_x = a->W / 64;
-    p.tiles_per_img = p.tiles_x * (a->H / 4);
-    p.ntiles = p.tiles_per_img * a->B;
-    p.tiles_per_xcd = (p.ntiles + 7) / 8;
-    const int per_xcd = p.tiles_per_xcd < wgs / 8 ? p.tiles_per_xcd : (wgs >= 8 ? wgs / 8 : 1);
+    head_set_tiles(p, a->B, a->H, a->W, 4);
+    const dim3 grid(head_walk_grid(p, wgs >= 8 ? wgs : 8));      // a cap below 8: one workgroup per XCD
     constexpr int LDS_B = 2 * 8 * 68 * 32 + 6 * 66 * 32;
-    hipStream_t st = (hipStream_t)stream;
     count_path(PATH_HBLOCK16);
-    if (a->out_h16) hipLaunchKernelGGL((hblock16_kernel<1>), dim3(per_xcd * 8), dim3(256), LDS_B, st, p);
-    else hipLaunchKernelGGL((hblock16_kernel<0>), dim3(per_xcd * 8), dim3(256), LDS_B, st, p);
-    SRBH_HIP(hipGetLastError());
-    return SRBH_OK;
+    return with_const<2>(a->out_h16 != 0, [&](auto o) { return launch<hblock16_kernel<decltype(o)::value>>(grid, LDS_B, (hipStream_t)stream, p); });
 }
 
 extern "C" int srbh_bn_finalize(const double* stats, int C, double count, const float* gamma, const float* beta,

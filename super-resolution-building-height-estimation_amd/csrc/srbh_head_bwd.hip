@@ -16,6 +16,7 @@
 //    dc = gamma*invstd * (dy - mean(dy) - xhat * mean(dy*xhat)); the ReLU mask of the block is applied on the fly.
 //  * small elementwise helpers: relu mask, in-place add, per-channel sum (bias grad), PixelShuffle(2) inverse.
 #include "srbh_internal.h"
+#include "srbh_head_walk.h"
 
 #include <type_traits>
 #include <vector>
@@ -104,8 +105,8 @@ __global__ __launch_bounds__(256) void hwgrad_f32_kernel(const WGParams p) {
 #pragma unroll
         for (int tp = 0; tp < TAPS; ++tp) acc[tp] = floatx4{0.f, 0.f, 0.f, 0.f};
         floatx4 acc2 = {0.f, 0.f, 0.f, 0.f};
-        // XCD-aware walk (see hconv_f32_kernel): XCD x = blockIdx % 8 owns the contiguous tiles [x*per_xcd, (x+1)*per_xcd), its
-        // gridDim/8 workgroups sweep them side by side, so the tiles' shared halo rows are re-read from that XCD's L2
+        // XCD-aware walk (explained in srbh_head_walk.h; written out here: with head_walk / head_tile this kernel's instructions change,
+        // profiles/head_launch_path_isa.txt)
         const int t_end = min((int)(blockIdx.x & 7) * p.tiles_per_xcd + p.tiles_per_xcd, p.ntiles);
         for (int t = (blockIdx.x & 7) * p.tiles_per_xcd + (blockIdx.x >> 3); t < t_end; t += gridDim.x >> 3) {
             const int img = t / p.tiles_per_img;
@@ -637,15 +638,7 @@ int hbwd16_wgs_cap() { static const int v = getenv("SRBH_HBWD16_WGS") ? atoi(get
 }  // namespace srbh
 
 namespace {
-// tile geometry of a walk over th x 64 tiles (th = HT_H; 4: hwgrad16_kernel, whose shapes have whole tiles only)
-void wg_set_tiles(WGParams& p, int B, int H, int W, int th) {
-    p.B = B; p.H = H; p.W = W;
-    p.tiles_x = (W + HT_W - 1) / HT_W;
-    p.tiles_per_img = p.tiles_x * ((H + th - 1) / th);
-    p.ntiles = p.tiles_per_img * B;
-    p.tiles_per_xcd = (p.ntiles + 7) / 8;
-}
-// workgroup columns (grid.x) of the 8 x 64 walks: a multiple of 8 (the same number of workgroups per XCD), at most 512
+// (tile geometry: head_set_tiles over HT_H x 64 tiles; 4 x 64 for hwgrad16_kernel)  workgroup columns (grid.x) of the 8 x 64 walks: a multiple of 8 (the same number of workgroups per XCD), at most 512
 int wg_columns(const WGParams& p) { return p.ntiles < 512 ? (p.ntiles + 7) / 8 * 8 : 512; }
 // sources, folded BN and dY of an NHWC call
 void wg_set_tensors(WGParams& p, const srbh_hwgrad_args* a) {
@@ -659,12 +652,7 @@ void wg_set_tensors(WGParams& p, const srbh_hwgrad_args* a) {
 }
 // one launch of a weight-gradient kernel with lds_bytes of dynamic LDS (its limit is raised once per device and kernel form)
 template <auto Kernel>
-int launch_wg(dim3 grid, int lds_bytes, hipStream_t st, const WGParams& p) {
-    SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)));
-    hipLaunchKernelGGL(Kernel, grid, dim3(256), lds_bytes, st, p);
-    SRBH_HIP(hipGetLastError());
-    return SRBH_OK;
-}
+int launch_wg(dim3 grid, int lds_bytes, hipStream_t st, const WGParams& p) { return launch<Kernel, true>(grid, lds_bytes, st, p); }
 
 int wgrad_impl(const srbh_hwgrad_args* a, void* stream, bool b16, const char* who) {
     SRBH_REQUIRE(a && a->src0 && a->dy && a->dw, "%s: null pointer", who);
@@ -677,7 +665,7 @@ int wgrad_impl(const srbh_hwgrad_args* a, void* stream, bool b16, const char* wh
     SRBH_REQUIRE((a->io & ~(SRBH_WG_SRC0_H16 | SRBH_WG_DY_B16)) == 0, "srbh_hconv_wgrad: unknown io bits");
     SRBH_REQUIRE(!a->io || b16, "srbh_hconv_wgrad_f32: 16-bit tensors in memory need the bf16-operand form (srbh_hconv_wgrad_b16)");
     const bool xs16 = (a->io & SRBH_WG_SRC0_H16) != 0, ds16 = (a->io & SRBH_WG_DY_B16) != 0;
-    wg_set_tiles(p, a->B, a->H, a->W, HT_H);
+    head_set_tiles(p, a->B, a->H, a->W, HT_H);
     hipStream_t st = (hipStream_t)stream;
     const int cin = a->c0 + a->c1;
     const int nob = (a->cout + 15) / 16;
@@ -687,7 +675,7 @@ int wgrad_impl(const srbh_hwgrad_args* a, void* stream, bool b16, const char* wh
     const bool can16 = (a->c0 & 3) == 0 && (a->c1 & 3) == 0 && (p.ld0 & 3) == 0 && (a->c1 == 0 || (p.ld1 & 3) == 0) && (a->cout & 15) == 0 &&
                        ((uintptr_t)a->src0 & 15) == 0 && ((uintptr_t)a->src1 & 15) == 0 && ((uintptr_t)a->dy & (ds16 ? 7 : 15)) == 0;
     // the dominant layer shape has its own double-buffered kernel (srbh_hwgrad16_kernel.h)
-    const int k16_wgs = hwgrad16_wgs_cap();   // 0 = never
+    const int k16_wgs = hwgrad16_wgs_cap();   // below 8 (0): not taken
     const bool narrow = a->cout < 16 && !ds16;          // conv_last (1 / 7 output channels): zero-padded to one 16-channel block while staged
     const bool k16 = b16 && k16_wgs >= 8 && k16_wgs <= WS_SLOTS && a->ksize == 3 && a->c0 == 16 && a->c1 == 0 && (a->cout == 16 || narrow) &&
                      (a->W & 63) == 0 && (a->H & 3) == 0 && (p.ld0 & 3) == 0 && ((uintptr_t)a->src0 & (xs16 ? 7 : 15)) == 0 &&
@@ -699,9 +687,8 @@ int wgrad_impl(const srbh_hwgrad_args* a, void* stream, bool b16, const char* wh
     static const int ob_inner = getenv("SRBH_WGRAD_OB_INNER") ? atoi(getenv("SRBH_WGRAD_OB_INNER")) : 1;      // 0: grid.y = output blocks (A/B aid)
     int rc;
     if (k16) {
-        wg_set_tiles(p, a->B, a->H, a->W, 4);
-        const int per_xcd = p.tiles_per_xcd < k16_wgs / 8 ? p.tiles_per_xcd : k16_wgs / 8;
-        gx = per_xcd * 8;
+        head_set_tiles(p, a->B, a->H, a->W, 4);
+        gx = head_walk_grid(p, k16_wgs);
         const dim3 grid(gx);
         constexpr int LDS_B = WG16T::LDS_B;
         if (narrow && xs16) rc = launch_wg<hwgrad16_kernel<1, 2>>(grid, LDS_B, st, p);
@@ -760,7 +747,7 @@ extern "C" int srbh_hconv_wgrad_entry_b16(const srbh_hwgrad_args* a3, const srbh
     WGParams p = {};
     wg_set_tensors(p, a3);
     p.dy2 = a1->dy; p.ws2 = a1->ws;
-    wg_set_tiles(p, a3->B, a3->H, a3->W, HT_H);
+    head_set_tiles(p, a3->B, a3->H, a3->W, HT_H);
     hipStream_t st = (hipStream_t)stream;
     const int cin = a3->c0 + a3->c1, nob = a3->cout / 16, nchunk = (cin + 15) / 16;
     const int gx = wg_columns(p);
@@ -810,7 +797,7 @@ extern "C" int srbh_act16_wgrad_b16(const void* x, int x_chunks_total, int cin, 
     const Act16Geo gx_ = act16_geo(B, x_chunks_total, H, W), gd = act16_geo(B, dy_chunks_total, H, W);
     p.x_img_b = gx_.img_b; p.x_plane_b = gx_.plane_b; p.x_row_b = gx_.row_b;
     p.dy_img_b = gd.img_b; p.dy_plane_b = gd.plane_b; p.dy_row_b = gd.row_b; p.dy_ch0 = dy_ch0;
-    wg_set_tiles(p, B, H, W, HT_H);
+    head_set_tiles(p, B, H, W, HT_H);
     hipStream_t st = (hipStream_t)stream;
     const int nob = cout / 16;
     int gx = wg_columns(p);
@@ -861,29 +848,18 @@ extern "C" int srbh_hbwd16(const srbh_hbwd16_args* a, void* stream) {
     p.w = a->w; p.dx = a->dx; p.dx_b16 = a->dx_b16; p.res = a->res;
     p.bstat_c = a->bstat_c; p.bstat_mean = a->bstat_mean; p.bstat_invstd = a->bstat_invstd; p.bstat_ms = a->bstat_ms; p.bstat_mh = a->bstat_mh;
     p.stats = a->stats; p.ws = a->ws; p.relu_bits = (const unsigned long long*)a->relu_bits;
-    p.B = a->B; p.H = a->H; p.W = a->W;
-    p.tiles_x = a->W / 64;
-    p.tiles_per_img = p.tiles_x * (a->H / 4);
-    p.ntiles = p.tiles_per_img * a->B;
-    p.tiles_per_xcd = (p.ntiles + 7) / 8;
+    head_set_tiles(p, a->B, a->H, a->W, 4);
     const int wgs = hbwd16_wgs_cap();
-    SRBH_REQUIRE(wgs >= 8 && wgs <= WS_SLOTS, "SRBH_HBWD16_WGS must be 8 .. %d", WS_SLOTS);
-    const int per_xcd = p.tiles_per_xcd < wgs / 8 ? p.tiles_per_xcd : wgs / 8;
-    const int gx = per_xcd * 8;
+    SRBH_REQUIRE(wgs >= 8 && wgs <= WS_SLOTS, "SRBH_HBWD16_WGS must be 8 .. %d", WS_SLOTS);      // a cap below 8: an argument error
+    const int gx = head_walk_grid(p, wgs);
     if (a->stats && !a->stats_clean) { if (int rc = zero_async(a->stats, (size_t)NSLOT * 2 * 16 * sizeof(double), st)) return rc; }
-#define SRBH_HB(B_, M_)                                                                                                            \
-    do {                                                                                                                      \
-        SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)hbwd16_kernel<B_, M_>, hipFuncAttributeMaxDynamicSharedMemorySize, HB16::LDS_B))); \
-        hipLaunchKernelGGL((hbwd16_kernel<B_, M_>), dim3(gx), dim3(256), HB16::LDS_B, st, p);                                   \
-    } while (0)
-    if (a->relu_bits && a->mask_scale) SRBH_HB(2, 1);
-    else if (a->relu_bits) SRBH_HB(2, 0);
-    else if (a->stats && a->mask_scale) SRBH_HB(1, 1);
-    else if (a->stats) SRBH_HB(1, 0);
-    else if (a->mask_scale) SRBH_HB(0, 1);
-    else SRBH_HB(0, 0);
-#undef SRBH_HB
-    SRBH_HIP(hipGetLastError());
+    // hbwd16_kernel<BS, MASK>: BS = 2 relu_bits form, 1 statistics epilogue, 0 none; MASK = the ReLU mask behind the BatchNorm
+    const int rc = with_const<3>(a->relu_bits ? 2 : a->stats ? 1 : 0, [&](auto b) {
+        return with_const<2>(a->mask_scale != nullptr, [&](auto m) {
+            return launch<hbwd16_kernel<decltype(b)::value, decltype(m)::value>, true>(dim3(gx), HB16::LDS_B, st, p);
+        });
+    });
+    if (rc) return rc;
     count_path(PATH_HBWD16);
     // the workgroups' weight-gradient partials -> dW (the ordered two-stage reduce of srbh_hconv_wgrad_b16; queued under srbh_hwgrad_defer)
     return reduce_partials(a->ws, a->dw, 9 * 256, gx, 1, 9, 16, 16, st);

@@ -37,9 +37,9 @@ struct WG16 {
 // (All forced inline.  The staging registers and accumulators are passed by reference; WGParams is passed BY VALUE: behind a reference to
 //  the kernel argument the compiler spent up to 5 % more instructions on the addresses of the entry forms (6 056 instead of 5 784 in
 //  hwgrad_entry_b16_kernel<0, 4>).  The flush takes the lane coordinates its kernel already holds.)
-// XCD-aware walk (see hconv_f32_kernel): XCD x = blockIdx % 8 owns the contiguous tiles [x*per_xcd, (x+1)*per_xcd), its gridDim/8
-// workgroups sweep them side by side, so the tiles' shared halo rows are re-read from that XCD's L2.  Returns the workgroup's first tile;
-// its next ones are wg_walk_step() apart, up to t_end.
+// XCD-aware walk: explained in srbh_head_walk.h, whose head_walk / head_tile are the same arithmetic behind a reference (this family stays
+// on its own by-value pair: by reference four of its forms change).  Returns the workgroup's first tile; its next ones are wg_walk_step()
+// apart, up to t_end.
 __device__ __forceinline__ int wg_walk(const WGParams p, int& t_end) {
     t_end = min((int)(blockIdx.x & 7) * p.tiles_per_xcd + p.tiles_per_xcd, p.ntiles);
     return (blockIdx.x & 7) * p.tiles_per_xcd + (blockIdx.x >> 3);

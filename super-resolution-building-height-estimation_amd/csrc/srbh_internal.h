@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
+#include <type_traits>
 #include <vector>
 #include "srbh.h"
 
@@ -63,6 +64,38 @@ int hip_fail(hipError_t e, const char* what);
             done_ |= 1ull << (dev_ & 63);                 \
         }                                                 \
     } while (0)
+
+// ---- host side of the head kernels' tile walks (device side: srbh_head_walk.h), for every head entry point, forward and backward ----
+// Tile geometry of a walk over th x 64 tiles.  P: a kernel parameter struct with B / H / W and the four tile fields.
+template <class P>
+inline void head_set_tiles(P& p, int B, int H, int W, int th) {
+    p.B = B; p.H = H; p.W = W;
+    p.tiles_x = (W + TILE_W - 1) / TILE_W;
+    p.tiles_per_img = p.tiles_x * ((H + th - 1) / th);
+    p.ntiles = p.tiles_per_img * B;
+    p.tiles_per_xcd = (p.ntiles + 7) / 8;
+}
+// Grid of a persistent walk under workgroup cap `cap`: min(tiles_per_xcd, cap / 8) workgroups on each of the 8 XCDs.  A cap below 8 gives no
+// workgroup: what an entry point does then (other form, error, one per XCD) is stated where it calls this.
+template <class P>
+inline int head_walk_grid(const P& p, int cap) { return (p.tiles_per_xcd < cap / 8 ? p.tiles_per_xcd : cap / 8) * 8; }
+// A run-time value v in 0 .. N-1 -> f(std::integral_constant<int, v>{}): how the head entry points turn flags into template arguments.  The
+// mapping stands in the caller's lambda; every combination of the nested calls is instantiated, and no other.
+template <int N, class F>
+inline int with_const(int v, F&& f) {
+    if constexpr (N == 1) return f(std::integral_constant<int, 0>{});
+    else return v == N - 1 ? f(std::integral_constant<int, N - 1>{}) : with_const<N - 1>(v, f);
+}
+// One launch of a head kernel (256 threads, lds_bytes of dynamic LDS, its parameter struct by value).  RAISE_LDS: the kernel's dynamic-LDS limit
+// is raised to lds_bytes first, once per device and kernel form -- a compile-time choice: a launch below the default 64 KiB pays no hipGetDevice.
+template <auto Kernel, bool RAISE_LDS = false, class P>
+inline int launch(dim3 grid, int lds_bytes, hipStream_t st, const P& p) {
+    if constexpr (RAISE_LDS)
+        SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)));
+    hipLaunchKernelGGL(Kernel, grid, dim3(256), lds_bytes, st, p);
+    SRBH_HIP(hipGetLastError());
+    return SRBH_OK;
+}
 
 // ACT16 geometry: [B][chunks][H+2][W+2][32] fp16 + read slack so tiled kernels may over-read.
 struct Act16Geo {
