@@ -23,113 +23,23 @@ namespace {
 using namespace srbh;
 
 constexpr int MAX_LDS_B = 160 * 1024 - 4096;
-constexpr int NW = 16;               // waves per workgroup of the BatchNorm kernels (1024 threads)
-constexpr int U = 4;                 // images per wave and round of global loads (16 waves x 4 = the whole batch of 64 in ONE round)
+constexpr int MID_LDS_CAP = MAX_LDS_B - 32 * 1024;     // dynamic LDS of the mid kernels: mbconv_mid_bwd_kernel<5> has 29 KB of static LDS (red + redw) beside it
 
-// (v_rcp_f32: 1 ulp; these kernels are bound by the instruction stream of one wave per SIMD, an IEEE division is ~10 instructions)
-__device__ __forceinline__ float sigmoidf(float z) { return __builtin_amdgcn_rcpf(1.f + __expf(-z)); }
-template <int ACT>
-__device__ __forceinline__ float act_f(float z) {
-    if (ACT == 1) return z * sigmoidf(z);
-    if (ACT == 2) return fmaxf(z, 0.f);
-    return z;
-}
-template <int ACT>
-__device__ __forceinline__ float act_grad(float z) {
-    if (ACT == 1) {
-        const float s = sigmoidf(z);
-        return s * (1.f + z * (1.f - s));
-    }
-    if (ACT == 2) return z > 0.f ? 1.f : 0.f;
-    return 1.f;
-}
+#include "srbh_mbconv_pieces.h"      // NW, U, act_f / act_grad, Vt, Geo, channel_sum, stage_sum / bn_stats, bn_dz / bn_bwd_sums / bn_dx, tap_reaches
 
-// sum over the lanes that share a channel (a run of `seg` = min(HW, 64) consecutive lanes, seg a power of two), then over the NW waves
-// through `red`; every thread returns the total of ITS channel.  RW == 64: a wave spans the CPW channels of the workgroup (channel
-// of a lane = lane / HW); RW == 256: the whole workgroup is one channel.  Deterministic order.
-__device__ __forceinline__ float channel_sum(float v, int seg, int slot, float (*red)[64], int wave, int lane) {
-    for (int o = 1; o < seg; o <<= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();                          // `red` may still be read from the previous reduction
-    if ((lane & (seg - 1)) == 0) red[wave][slot] = v;
-    __syncthreads();
-    float a = 0.f, b = 0.f;
-#pragma unroll
-    for (int w = 0; w < NW; w += 2) {
-        a += red[w][slot];
-        b += red[w + 1][slot];
-    }
-    return a + b;
-}
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-template <int VEC> struct Vt { float v[VEC]; };
-template <int VEC> __device__ __forceinline__ Vt<VEC> ldv(const float* p) {
-    Vt<VEC> r;
-    if (VEC == 4) {
-        const floatx4 t = *(const floatx4*)p;
-        r.v[0] = t[0]; r.v[1 % VEC] = t[1]; r.v[2 % VEC] = t[2]; r.v[3 % VEC] = t[3];
-    } else {
-        r.v[0] = *p;
-    }
-    return r;
-}
-template <int VEC> __device__ __forceinline__ void stv(float* p, const Vt<VEC>& r) {
-    if (VEC == 4) *(floatx4*)p = floatx4{r.v[0], r.v[1 % VEC], r.v[2 % VEC], r.v[3 % VEC]};
-    else *p = r.v[0];
-}
-template <int VEC> __device__ __forceinline__ Vt<VEC> zerov() {
-    Vt<VEC> r;
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) r.v[k] = 0.f;
-    return r;
-}
-
-// Geometry shared by the forward and the backward kernel.  A workgroup owns a run of 64 * VEC contiguous floats per image: VEC = 1 --
-// CPW = 64 / HW adjacent channels of HW <= 64 elements; VEC = 4 -- one channel of 256 elements, a float4 per lane.  Wave w takes the
-// images w, w + NW, ...; a lane keeps the same position of the run for every image.
-struct FwdP {
-    const float* x; float* y;
-    const float* gamma; const float* beta;
-    float* running_mean; float* running_var;
-    float* save_mean; float* save_invstd;
-    float* pooled; const float* res; const float* drop;
-    float momentum, eps;
-    int B, C, HW;
-};
-
+// The kernels take the public argument structs (srbh.h) as they are, plus what the host derived from them.  Everything the later phases need --
+// affine parameters, running statistics, the first round of the skip connection -- is requested before the reductions.
 template <int ACT, int VEC>
-__global__ __launch_bounds__(64 * NW) void bn_act_train_fwd_kernel(const FwdP p) {
+__global__ __launch_bounds__(64 * NW) void bn_act_train_fwd_kernel(const srbh_bnact_args p) {
     extern __shared__ __attribute__((aligned(16))) float cache[];      // [B][64 * VEC]
     __shared__ float red[NW][64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int HW = p.HW, RW = 64 * VEC;
-    const int seg = (VEC == 4 || HW >= 64) ? 64 : HW;
-    const int slot = VEC == 4 ? 0 : lane / HW;
-    const int c0 = blockIdx.x * (RW / HW), c = c0 + slot;
-    const bool cok = c < p.C;
-    const float invN = 1.f / ((float)p.B * (float)HW);
-    const long off = (long)c0 * HW + lane * VEC, bstride = (long)p.C * HW;
-    // These kernels are LATENCY chains, not bandwidth: a workgroup moves 16-64 KB.  Every global pass is therefore issued U images at
-    // a time (a plain loop leaves one load in flight per lane: measured 12-16 us per launch), and everything the later phases
-    // need -- affine parameters, running statistics, the first round of the skip connection -- is requested before the reductions.
+    const Geo<VEC> g(p.B, p.C, p.HW);
+    const int lane = g.lane, wave = g.wave, seg = g.seg, c = g.c;
+    const bool cok = g.cok;
+    const long off = g.off, bstride = g.bstride;
     const float gam = cok ? p.gamma[c] : 0.f, bet = cok ? p.beta[c] : 0.f;
     const float rm0 = (cok && p.running_mean) ? p.running_mean[c] : 0.f, rv0 = (cok && p.running_mean) ? p.running_var[c] : 0.f;
-    float s = 0.f;
-    for (int b0 = wave; b0 < p.B; b0 += NW * U) {
-        Vt<VEC> v[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int b = b0 + NW * u;
-            v[u] = (cok && b < p.B) ? ldv<VEC>(p.x + b * bstride + off) : zerov<VEC>();
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int b = b0 + NW * u;
-            if (b < p.B) stv<VEC>(cache + (b * 64 + lane) * VEC, v[u]);
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) s += v[u].v[k];
-        }
-    }
+    const float s = stage_sum(g, p.x, cache, p.B);
     Vt<VEC> r0[U];
     float dr0[U];
 #pragma unroll
@@ -138,25 +48,8 @@ __global__ __launch_bounds__(64 * NW) void bn_act_train_fwd_kernel(const FwdP p)
         r0[u] = (p.res && cok && b < p.B) ? ldv<VEC>(p.res + b * bstride + off) : zerov<VEC>();
         dr0[u] = (p.drop && b < p.B) ? p.drop[b] : 1.f;
     }
-    const float mean = channel_sum(s, seg, slot, red, wave, lane) * invN;
-    float q = 0.f;
-    for (int b = wave; b < p.B; b += NW) {
-        const Vt<VEC> v = ldv<VEC>(cache + (b * 64 + lane) * VEC);
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) q = fmaf(v.v[k] - mean, v.v[k] - mean, q);
-    }
-    const float var = channel_sum(q, seg, slot, red, wave, lane) * invN;       // biased, as F.batch_norm normalises
-    const float invstd = 1.f / sqrtf(var + p.eps);
-    if (cok && wave == 0 && (lane & (seg - 1)) == 0) {
-        p.save_mean[c] = mean;
-        p.save_invstd[c] = invstd;
-        if (p.running_mean) {
-            const float n = (float)p.B * (float)HW;
-            p.running_mean[c] = (1.f - p.momentum) * rm0 + p.momentum * mean;
-            p.running_var[c] = (1.f - p.momentum) * rv0 + p.momentum * (n > 1.f ? var * n / (n - 1.f) : var);
-        }
-    }
-    const float scale = gam * invstd, shift = bet - mean * scale;
+    const BnStat st = bn_stats<VEC, true>(g, cache, p.B, s, p.eps, BnStatOut{p.save_mean, p.save_invstd, p.running_mean, p.running_var, rm0, rv0, p.momentum}, red);
+    const float scale = gam * st.invstd, shift = bet - st.mean * scale;
     for (int b0 = wave; b0 < p.B; b0 += NW * U) {
         Vt<VEC> r[U];
         float dr[U];
@@ -175,7 +68,7 @@ __global__ __launch_bounds__(64 * NW) void bn_act_train_fwd_kernel(const FwdP p)
         for (int u = 0; u < U; ++u) {
             const int b = b0 + NW * u;
             if (b >= p.B) continue;                                // (uniform per wave: b depends on the wave only)
-            Vt<VEC> a = ldv<VEC>(cache + (b * 64 + lane) * VEC);
+            Vt<VEC> a = ldv<VEC>(cache + g.at(b));
             float w = 0.f;
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
@@ -185,34 +78,22 @@ __global__ __launch_bounds__(64 * NW) void bn_act_train_fwd_kernel(const FwdP p)
             if (cok) stv<VEC>(p.y + b * bstride + off, a);
             if (p.pooled) {
                 for (int o = 1; o < seg; o <<= 1) w += __shfl_xor(w, o, 64);
-                if (cok && (lane & (seg - 1)) == 0) p.pooled[(long)b * p.C + c] = w / (float)HW;
+                if (cok && g.pos == 0) p.pooled[(long)b * p.C + c] = w / (float)p.HW;
             }
         }
     }
 }
 
-struct BwdP {
-    const float* dy; const float* x;
-    const float* gamma; const float* beta; const float* save_mean; const float* save_invstd;
-    const float* gate; const float* dpooled; const float* drop;
-    float* dx; float* dgamma; float* dbeta;
-    int B, C, HW;
-};
-
 template <int ACT, int VEC>
-__global__ __launch_bounds__(64 * NW) void bn_act_train_bwd_kernel(const BwdP p) {
+__global__ __launch_bounds__(64 * NW) void bn_act_train_bwd_kernel(const srbh_bnact_bwd_args p) {
     extern __shared__ __attribute__((aligned(16))) float cache[];      // [B][64 * VEC] dz | [B][64 * VEC] xhat
     __shared__ float red[NW][64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int HW = p.HW, RW = 64 * VEC;
-    const int seg = (VEC == 4 || HW >= 64) ? 64 : HW;
-    const int slot = VEC == 4 ? 0 : lane / HW;
-    const int c0 = blockIdx.x * (RW / HW), c = c0 + slot;
-    const bool cok = c < p.C;
-    const float invN = 1.f / ((float)p.B * (float)HW), invHW = 1.f / (float)HW;
-    const float mean = cok ? p.save_mean[c] : 0.f, invstd = cok ? p.save_invstd[c] : 0.f;
-    const float g = cok ? p.gamma[c] : 0.f, be = cok ? p.beta[c] : 0.f;
-    const long off = (long)c0 * HW + lane * VEC, bstride = (long)p.C * HW;
+    const Geo<VEC> g(p.B, p.C, p.HW);
+    const int wave = g.wave, c = g.c;
+    const bool cok = g.cok;
+    const long off = g.off, bstride = g.bstride;
+    const float invHW = 1.f / (float)p.HW;
+    const BnNorm m{cok ? p.save_mean[c] : 0.f, cok ? p.save_invstd[c] : 0.f, cok ? p.gamma[c] : 0.f, cok ? p.beta[c] : 0.f};
     float* const xhc = cache + p.B * 64 * VEC;
     float s1 = 0.f, s2 = 0.f;
     for (int b0 = wave; b0 < p.B; b0 += NW * U) {
@@ -235,30 +116,22 @@ __global__ __launch_bounds__(64 * NW) void bn_act_train_bwd_kernel(const BwdP p)
             Vt<VEC> dz, xh;
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
-                xh.v[k] = (xv[u].v[k] - mean) * invstd;
-                const float d = fmaf(dv[u].v[k], gt[u], dpo[u]) * dr[u];
-                dz.v[k] = cok ? d * act_grad<ACT>(fmaf(xh.v[k], g, be)) : 0.f;
-                s2 = fmaf(dz.v[k], xh.v[k], s2);
-                s1 += dz.v[k];
+                xh.v[k] = bn_xhat(xv[u].v[k], m);
+                dz.v[k] = cok ? bn_dz<ACT, true, true>(xh.v[k], dv[u].v[k], m, gt[u], dpo[u], dr[u]) : 0.f;      // (gate / drop are run-time here: 1, 0, 1 without)
+                bn_bwd_accum(dz.v[k], xh.v[k], s1, s2);
             }
-            stv<VEC>(cache + (b * 64 + lane) * VEC, dz);
-            stv<VEC>(xhc + (b * 64 + lane) * VEC, xh);
+            stv<VEC>(cache + g.at(b), dz);
+            stv<VEC>(xhc + g.at(b), xh);
         }
     }
-    const float sum_dz = channel_sum(s1, seg, slot, red, wave, lane);
-    const float sum_dzx = channel_sum(s2, seg, slot, red, wave, lane);
-    if (cok && wave == 0 && (lane & (seg - 1)) == 0) {
-        p.dbeta[c] = sum_dz;
-        p.dgamma[c] = sum_dzx;
-    }
+    const BnBwdK kk = bn_bwd_sums(g, s1, s2, m.g, m.invstd, p.dbeta, p.dgamma, red);
     if (!p.dx) return;
-    const float k1 = sum_dz * invN, k2 = sum_dzx * invN, gi = g * invstd;
     for (int b = wave; b < p.B; b += NW) {
         if (!cok) continue;
-        Vt<VEC> dz = ldv<VEC>(cache + (b * 64 + lane) * VEC);
-        const Vt<VEC> xh = ldv<VEC>(xhc + (b * 64 + lane) * VEC);
+        Vt<VEC> dz = ldv<VEC>(cache + g.at(b));
+        const Vt<VEC> xh = ldv<VEC>(xhc + g.at(b));
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) dz.v[k] = gi * (dz.v[k] - k1 - xh.v[k] * k2);
+        for (int k = 0; k < VEC; ++k) dz.v[k] = bn_dx(dz.v[k], xh.v[k], kk);
         stv<VEC>(p.dx + b * bstride + off, dz);
     }
 }
@@ -271,143 +144,81 @@ __global__ __launch_bounds__(64 * NW) void bn_act_train_bwd_kernel(const BwdP p)
 // the backward (bn_act backward with the excite gate, depthwise data and weight gradient, bn_act backward) need nothing from another
 // workgroup: one read of the expand conv's output, one write each of the depthwise output (kept for the backward) and of y; the
 // backward reads both back, recomputes SiLU(bn0(.)) instead of keeping it, and writes only the gradient of the expand conv's output.
-// Planes of 2x2, 4x4 and 8x8 (blocks 6..31 of EfficientNet-B4 at 64x64 tiles, without the three stride-2 blocks).
-struct MidFwdP {
-    const float* e_pre; const float* wdw;
-    const float* g0; const float* b0; float* rm0; float* rv0; float* mean0; float* invstd0;
-    const float* g1; const float* b1; float* rm1; float* rv1; float* mean1; float* invstd1;
-    float* d_pre; float* y; float* pooled;
-    float mom0, eps0, mom1, eps1;
-    int B, C, HW, logw;
-};
-
-// two-pass statistics of this thread's channel over cache[b][lane], b = wave, wave + NW, ... (as bn_act_train_fwd_kernel)
-__device__ __forceinline__ void channel_stats(const float* cache, int B, float s, float invN, float eps, int seg, int slot, float (*red)[64],
-                                              int wave, int lane, float& mean, float& var, float& invstd) {
-    mean = channel_sum(s, seg, slot, red, wave, lane) * invN;
-    float q = 0.f;
-    for (int b = wave; b < B; b += NW) {
-        const float v = cache[b * 64 + lane];
-        q = fmaf(v - mean, v - mean, q);
-    }
-    var = channel_sum(q, seg, slot, red, wave, lane) * invN;
-    invstd = 1.f / sqrtf(var + eps);
-}
-
+// Planes of 2x2, 4x4 and 8x8 (blocks 6..31 of EfficientNet-B4 at 64x64 tiles, without the three stride-2 blocks).  HW = H * W, W = 1 << logw.
 template <int K>
-__global__ __launch_bounds__(64 * NW) void mbconv_mid_fwd_kernel(const MidFwdP p) {
+__global__ __launch_bounds__(64 * NW) void mbconv_mid_fwd_kernel(const srbh_mbmid_args p, int HW, int logw) {
     extern __shared__ __attribute__((aligned(16))) float cache[];      // [B][64] e_pre -> SiLU(bn0) | [B][64] depthwise output
     __shared__ float red[NW][64];
     constexpr int R = K / 2, KK = K * K;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int HW = p.HW, W = 1 << p.logw;
-    const int seg = HW >= 64 ? 64 : HW;
-    const int slot = lane / HW, pos = lane & (HW - 1), py = pos >> p.logw, px = pos & (W - 1);
-    const int c0 = blockIdx.x * (64 / HW), c = c0 + slot;
-    const bool cok = c < p.C;
-    const float invN = 1.f / ((float)p.B * (float)HW), n = (float)p.B * (float)HW;
-    const long off = (long)c0 * HW + lane, bstride = (long)p.C * HW;
+    const Geo<1> g(p.B, p.C, HW);
+    const int wave = g.wave, c = g.c, W = 1 << logw, py = g.pos >> logw, px = g.pos & (W - 1);
+    const bool cok = g.cok;
+    const long off = g.off, bstride = g.bstride;
     float* const dch = cache + p.B * 64;
-    const float g0 = cok ? p.g0[c] : 0.f, b0 = cok ? p.b0[c] : 0.f, g1 = cok ? p.g1[c] : 0.f, b1 = cok ? p.b1[c] : 0.f;
-    const float rm0 = cok ? p.rm0[c] : 0.f, rv0 = cok ? p.rv0[c] : 0.f, rm1 = cok ? p.rm1[c] : 0.f, rv1 = cok ? p.rv1[c] : 0.f;
+    const float g0 = cok ? p.gamma0[c] : 0.f, b0 = cok ? p.beta0[c] : 0.f, g1 = cok ? p.gamma1[c] : 0.f, b1 = cok ? p.beta1[c] : 0.f;
+    const float rm0 = cok ? p.running_mean0[c] : 0.f, rv0 = cok ? p.running_var0[c] : 0.f;
+    const float rm1 = cok ? p.running_mean1[c] : 0.f, rv1 = cok ? p.running_var1[c] : 0.f;
     float wk[KK];
 #pragma unroll
     for (int k = 0; k < KK; ++k) wk[k] = cok ? p.wdw[(long)c * KK + k] : 0.f;
     // ---- BatchNorm0: statistics of the expand conv's output
-    float s = 0.f;
-    for (int b0i = wave; b0i < p.B; b0i += NW * U) {
-        float v[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int b = b0i + NW * u;
-            v[u] = (cok && b < p.B) ? p.e_pre[b * bstride + off] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int b = b0i + NW * u;
-            if (b < p.B) cache[b * 64 + lane] = v[u];
-            s += v[u];
-        }
-    }
-    float mean, var, invstd;
-    channel_stats(cache, p.B, s, invN, p.eps0, seg, slot, red, wave, lane, mean, var, invstd);
-    if (cok && wave == 0 && pos == 0) {
-        p.mean0[c] = mean;
-        p.invstd0[c] = invstd;
-        p.rm0[c] = (1.f - p.mom0) * rm0 + p.mom0 * mean;
-        p.rv0[c] = (1.f - p.mom0) * rv0 + p.mom0 * (n > 1.f ? var * n / (n - 1.f) : var);
-    }
+    float s = stage_sum(g, p.e_pre, cache, p.B);
+    BnStat st = bn_stats<1, false>(g, cache, p.B, s, p.eps0, BnStatOut{p.mean0, p.invstd0, p.running_mean0, p.running_var0, rm0, rv0, p.momentum0}, red);
     {
-        const float sc = g0 * invstd, sh = b0 - mean * sc;
-        for (int b = wave; b < p.B; b += NW) cache[b * 64 + lane] = cok ? act_f<1>(fmaf(cache[b * 64 + lane], sc, sh)) : 0.f;
+        const float sc = g0 * st.invstd, sh = b0 - st.mean * sc;
+        for (int b = wave; b < p.B; b += NW) cache[g.at(b)] = cok ? act_f<1>(fmaf(cache[g.at(b)], sc, sh)) : 0.f;
     }
     __syncthreads();
-    // ---- depthwise K x K, stride 1, zero padding R: neighbours of this lane's pixel inside its own plane
+    // ---- depthwise K x K, stride 1, zero padding K / 2: neighbours of this lane's pixel inside its own plane
     s = 0.f;
     for (int b = wave; b < p.B; b += NW) {
-        const float* pl = cache + b * 64 + slot * HW;
+        const float* pl = cache + b * 64 + g.slot * HW;
         float acc = 0.f;
 #pragma unroll
         for (int dy = 0; dy < K; ++dy) {
-            if (dy - R >= W || R - dy >= W) continue;       // (uniform: a tap further out than the plane is wide never lands inside it -- 16 of the 25 taps at 2x2)
+            if (!tap_reaches<K>(dy, W)) continue;
             const int yy = py + dy - R;
 #pragma unroll
             for (int dx = 0; dx < K; ++dx) {
-                if (dx - R >= W || R - dx >= W) continue;
+                if (!tap_reaches<K>(dx, W)) continue;
                 const int xx = px + dx - R;
-                if ((unsigned)yy < (unsigned)W && (unsigned)xx < (unsigned)W) acc = fmaf(wk[dy * K + dx], pl[(yy << p.logw) + xx], acc);
+                if ((unsigned)yy < (unsigned)W && (unsigned)xx < (unsigned)W) acc = fmaf(wk[dy * K + dx], pl[(yy << logw) + xx], acc);
             }
         }
-        dch[b * 64 + lane] = acc;
+        dch[g.at(b)] = acc;
         if (cok) p.d_pre[b * bstride + off] = acc;
         s += acc;
     }
     // ---- BatchNorm1 + SiLU + plane means
-    channel_stats(dch, p.B, s, invN, p.eps1, seg, slot, red, wave, lane, mean, var, invstd);
-    if (cok && wave == 0 && pos == 0) {
-        p.mean1[c] = mean;
-        p.invstd1[c] = invstd;
-        p.rm1[c] = (1.f - p.mom1) * rm1 + p.mom1 * mean;
-        p.rv1[c] = (1.f - p.mom1) * rv1 + p.mom1 * (n > 1.f ? var * n / (n - 1.f) : var);
-    }
-    const float sc1 = g1 * invstd, sh1 = b1 - mean * sc1, invHW = 1.f / (float)HW;
+    st = bn_stats<1, false>(g, dch, p.B, s, p.eps1, BnStatOut{p.mean1, p.invstd1, p.running_mean1, p.running_var1, rm1, rv1, p.momentum1}, red);
+    const float sc1 = g1 * st.invstd, sh1 = b1 - st.mean * sc1, invHW = 1.f / (float)HW;
     for (int b = wave; b < p.B; b += NW) {
-        const float v = act_f<1>(fmaf(dch[b * 64 + lane], sc1, sh1));
+        const float v = act_f<1>(fmaf(dch[g.at(b)], sc1, sh1));
         if (cok) p.y[b * bstride + off] = v;
         float w = v;
-        for (int o = 1; o < seg; o <<= 1) w += __shfl_xor(w, o, 64);
-        if (cok && pos == 0) p.pooled[(long)b * p.C + c] = w * invHW;
+        for (int o = 1; o < g.seg; o <<= 1) w += __shfl_xor(w, o, 64);
+        if (cok && g.pos == 0) p.pooled[(long)b * p.C + c] = w * invHW;
     }
 }
 
-struct MidBwdP {
-    const float* dout; const float* gate; const float* dpooled;      // gradient of y * gate; excite gate [B][C]; gradient of the plane means [B][C]
-    const float* d_pre; const float* e_pre; const float* wdw;
-    const float* g0; const float* b0; const float* mean0; const float* invstd0;
-    const float* g1; const float* b1; const float* mean1; const float* invstd1;
-    float* de_pre; float* dwdw; float* dg0; float* db0; float* dg1; float* db1;
-    int B, C, HW, logw;
-};
-
+// dout = the gradient of y * gate; gate = the excite gate [B][C]; dpooled = the gradient of the plane means [B][C]
 template <int K>
-__global__ __launch_bounds__(64 * NW) void mbconv_mid_bwd_kernel(const MidBwdP p) {
+__global__ __launch_bounds__(64 * NW) void mbconv_mid_bwd_kernel(const srbh_mbmid_bwd_args p, int HW, int logw) {
     extern __shared__ __attribute__((aligned(16))) float cache[];      // A: dz1 -> dd_pre | Bc: xhat1 -> SiLU(bn0) -> dz0 | Cc: xhat0
     __shared__ float red[NW][64];
     __shared__ float redw[NW][K * K][16];
     constexpr int R = K / 2, KK = K * K;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int HW = p.HW, W = 1 << p.logw;
-    const int seg = HW >= 64 ? 64 : HW;
-    const int slot = lane / HW, pos = lane & (HW - 1), py = pos >> p.logw, px = pos & (W - 1);
-    const int cpw = 64 / HW, c0 = blockIdx.x * cpw, c = c0 + slot;
-    const bool cok = c < p.C;
-    const float invN = 1.f / ((float)p.B * (float)HW), invHW = 1.f / (float)HW;
-    const long off = (long)c0 * HW + lane, bstride = (long)p.C * HW;
+    const Geo<1> g(p.B, p.C, HW);
+    const int t = threadIdx.x, wave = g.wave, c = g.c, c0 = g.c0, cpw = 64 / HW, W = 1 << logw, py = g.pos >> logw, px = g.pos & (W - 1);
+    const bool cok = g.cok;
+    const long off = g.off, bstride = g.bstride;
+    const float invHW = 1.f / (float)HW;
     float* const A = cache;
     float* const Bc = cache + p.B * 64;
     float* const Cc = cache + 2 * p.B * 64;
-    const float g0 = cok ? p.g0[c] : 0.f, b0 = cok ? p.b0[c] : 0.f, g1 = cok ? p.g1[c] : 0.f, b1 = cok ? p.b1[c] : 0.f;
+    const float g0 = cok ? p.gamma0[c] : 0.f, b0 = cok ? p.beta0[c] : 0.f, g1 = cok ? p.gamma1[c] : 0.f, b1 = cok ? p.beta1[c] : 0.f;
     const float m0 = cok ? p.mean0[c] : 0.f, i0 = cok ? p.invstd0[c] : 0.f, m1 = cok ? p.mean1[c] : 0.f, i1 = cok ? p.invstd1[c] : 0.f;
+    const BnNorm n0{m0, i0, g0, b0}, n1{m1, i1, g1, b1};
     float wk[KK];
 #pragma unroll
     for (int k = 0; k < KK; ++k) wk[k] = cok ? p.wdw[(long)c * KK + k] : 0.f;
@@ -429,28 +240,19 @@ __global__ __launch_bounds__(64 * NW) void mbconv_mid_bwd_kernel(const MidBwdP p
         for (int u = 0; u < U; ++u) {
             const int b = b0i + NW * u;
             if (b >= p.B) continue;
-            const float xh = (xv[u] - m1) * i1;
-            const float dz = cok ? fmaf(dv[u], gt[u], dpo[u]) * act_grad<1>(fmaf(xh, g1, b1)) : 0.f;
-            s2 = fmaf(dz, xh, s2);
-            s1 += dz;
-            A[b * 64 + lane] = dz;
-            Bc[b * 64 + lane] = xh;
-            Cc[b * 64 + lane] = (ev[u] - m0) * i0;                 // xhat0 (the depthwise conv's input is SiLU(xhat0 g0 + b0))
+            const float xh = bn_xhat(xv[u], n1);
+            const float dz = cok ? bn_dz<1, true, false>(xh, dv[u], n1, gt[u], dpo[u], 1.f) : 0.f;
+            bn_bwd_accum(dz, xh, s1, s2);
+            A[g.at(b)] = dz;
+            Bc[g.at(b)] = xh;
+            Cc[g.at(b)] = bn_xhat(ev[u], n0);                       // xhat0 (the depthwise conv's input is SiLU(xhat0 g0 + b0))
         }
     }
-    float sum_dz = channel_sum(s1, seg, slot, red, wave, lane);
-    float sum_dzx = channel_sum(s2, seg, slot, red, wave, lane);
-    if (cok && wave == 0 && pos == 0) {
-        p.db1[c] = sum_dz;
-        p.dg1[c] = sum_dzx;
-    }
-    {
-        const float k1 = sum_dz * invN, k2 = sum_dzx * invN, gi = g1 * i1;
-        for (int b = wave; b < p.B; b += NW) {
-            const float dd = cok ? gi * (A[b * 64 + lane] - k1 - Bc[b * 64 + lane] * k2) : 0.f;     // gradient of the depthwise output
-            A[b * 64 + lane] = dd;
-            Bc[b * 64 + lane] = cok ? act_f<1>(fmaf(Cc[b * 64 + lane], g0, b0)) : 0.f;              // the depthwise input, recomputed
-        }
+    BnBwdK kk = bn_bwd_sums(g, s1, s2, g1, i1, p.dbeta1, p.dgamma1, red);
+    for (int b = wave; b < p.B; b += NW) {
+        const float dd = cok ? bn_dx(A[g.at(b)], Bc[g.at(b)], kk) : 0.f;                     // gradient of the depthwise output
+        A[g.at(b)] = dd;
+        Bc[g.at(b)] = cok ? act_f<1>(fmaf(Cc[g.at(b)], g0, b0)) : 0.f;                       // the depthwise input, recomputed
     }
     __syncthreads();
     // ---- depthwise weight gradient: dw[c][tap] = sum over (b, p) of dd[b][c][p] * in[b][c][p + tap]
@@ -459,27 +261,26 @@ __global__ __launch_bounds__(64 * NW) void mbconv_mid_bwd_kernel(const MidBwdP p
 #pragma unroll
         for (int k = 0; k < KK; ++k) pw[k] = 0.f;
         for (int b = wave; b < p.B; b += NW) {
-            const float dd = A[b * 64 + lane];
-            const float* pl = Bc + b * 64 + slot * HW;
+            const float dd = A[g.at(b)];
+            const float* pl = Bc + b * 64 + g.slot * HW;
 #pragma unroll
             for (int dy = 0; dy < K; ++dy) {
-                if (dy - R >= W || R - dy >= W) continue;
+                if (!tap_reaches<K>(dy, W)) continue;
                 const int yy = py + dy - R;
 #pragma unroll
                 for (int dx = 0; dx < K; ++dx) {
-                    if (dx - R >= W || R - dx >= W) continue;
+                    if (!tap_reaches<K>(dx, W)) continue;
                     const int xx = px + dx - R;
-                    if ((unsigned)yy < (unsigned)W && (unsigned)xx < (unsigned)W) pw[dy * K + dx] = fmaf(dd, pl[(yy << p.logw) + xx], pw[dy * K + dx]);
+                    if ((unsigned)yy < (unsigned)W && (unsigned)xx < (unsigned)W) pw[dy * K + dx] = fmaf(dd, pl[(yy << logw) + xx], pw[dy * K + dx]);
                 }
             }
         }
 #pragma unroll
         for (int k = 0; k < KK; ++k) {
             float v = pw[k];
-            const int ty = k / K - R, tx = k % K - R;
-            if (ty < W && -ty < W && tx < W && -tx < W)          // (uniform; a tap that never lands inside the plane stays 0)
-                for (int o = 1; o < seg; o <<= 1) v += __shfl_xor(v, o, 64);
-            if (pos == 0) redw[wave][k][slot] = v;
+            if (tap_reaches<K>(k / K, W) && tap_reaches<K>(k % K, W))          // (uniform; a tap that never lands inside the plane stays 0)
+                for (int o = 1; o < g.seg; o <<= 1) v += __shfl_xor(v, o, 64);
+            if (g.pos == 0) redw[wave][k][g.slot] = v;
         }
         __syncthreads();
         for (int u = t; u < KK * cpw; u += 64 * NW) {
@@ -498,37 +299,28 @@ __global__ __launch_bounds__(64 * NW) void mbconv_mid_bwd_kernel(const MidBwdP p
     s2 = 0.f;
     __syncthreads();              // (Bc is overwritten below: every wave is past the weight gradient's reads)
     for (int b = wave; b < p.B; b += NW) {
-        const float* pl = A + b * 64 + slot * HW;
+        const float* pl = A + b * 64 + g.slot * HW;
         float acc = 0.f;
 #pragma unroll
-        for (int dy = 0; dy < K; ++dy) {
-            if (dy - R >= W || R - dy >= W) continue;
+        for (int dy = 0; dy < K; ++dy) {                      // (the mirrored walk: py - dy + R)
+            if (!tap_reaches<K>(dy, W)) continue;
             const int yy = py - dy + R;
 #pragma unroll
             for (int dx = 0; dx < K; ++dx) {
-                if (dx - R >= W || R - dx >= W) continue;
+                if (!tap_reaches<K>(dx, W)) continue;
                 const int xx = px - dx + R;
-                if ((unsigned)yy < (unsigned)W && (unsigned)xx < (unsigned)W) acc = fmaf(wk[dy * K + dx], pl[(yy << p.logw) + xx], acc);
+                if ((unsigned)yy < (unsigned)W && (unsigned)xx < (unsigned)W) acc = fmaf(wk[dy * K + dx], pl[(yy << logw) + xx], acc);
             }
         }
-        const float xh = Cc[b * 64 + lane];
-        const float dz = cok ? acc * act_grad<1>(fmaf(xh, g0, b0)) : 0.f;
-        s2 = fmaf(dz, xh, s2);
-        s1 += dz;
-        Bc[b * 64 + lane] = dz;          // (own element)
+        const float xh = Cc[g.at(b)];
+        const float dz = cok ? bn_dz<1, false, false>(xh, acc, n0, 0.f, 0.f, 1.f) : 0.f;
+        bn_bwd_accum(dz, xh, s1, s2);
+        Bc[g.at(b)] = dz;          // (own element)
     }
-    sum_dz = channel_sum(s1, seg, slot, red, wave, lane);
-    sum_dzx = channel_sum(s2, seg, slot, red, wave, lane);
-    if (cok && wave == 0 && pos == 0) {
-        p.db0[c] = sum_dz;
-        p.dg0[c] = sum_dzx;
-    }
+    kk = bn_bwd_sums(g, s1, s2, g0, i0, p.dbeta0, p.dgamma0, red);
     if (!p.de_pre) return;
-    {
-        const float k1 = sum_dz * invN, k2 = sum_dzx * invN, gi = g0 * i0;
-        for (int b = wave; b < p.B; b += NW)
-            if (cok) p.de_pre[b * bstride + off] = gi * (Bc[b * 64 + lane] - k1 - Cc[b * 64 + lane] * k2);
-    }
+    for (int b = wave; b < p.B; b += NW)
+        if (cok) p.de_pre[b * bstride + off] = bn_dx(Bc[g.at(b)], Cc[g.at(b)], kk);
 }
 
 // squeeze-excite backward, step 1: draw[b][c] = sum over the plane of dout * y, y = act(bn(x)) recomputed from the saved conv output
@@ -858,7 +650,7 @@ __global__ __launch_bounds__(256) void bn_large_stats_kernel(const float* __rest
 }
 
 template <int ACT>
-__global__ __launch_bounds__(256) void bn_large_apply_kernel(const FwdP p, const double* __restrict__ part, int S) {
+__global__ __launch_bounds__(256) void bn_large_apply_kernel(const srbh_bnact_args p, const double* __restrict__ part, int S) {
     __shared__ double red[4];
     const long pl = blockIdx.x;
     const int c = (int)(pl % p.C), t = threadIdx.x, n4 = p.HW >> 2;
@@ -875,10 +667,7 @@ __global__ __launch_bounds__(256) void bn_large_apply_kernel(const FwdP p, const
     if (b == 0 && t == 0) {
         p.save_mean[c] = mean;
         p.save_invstd[c] = invstd;
-        if (p.running_mean) {
-            p.running_mean[c] = (1.f - p.momentum) * p.running_mean[c] + p.momentum * mean;
-            p.running_var[c] = (1.f - p.momentum) * p.running_var[c] + p.momentum * (float)(n > 1.0 ? dvar * n / (n - 1.0) : dvar);
-        }
+        if (p.running_mean) update_running(p.running_mean + c, p.running_var + c, p.running_mean[c], p.running_var[c], p.momentum, mean, dvar, n);
     }
     const float scale = p.gamma[c] * invstd, shift = p.beta[c] - mean * scale, dr = p.drop ? p.drop[b] : 1.f;
     const floatx4* xp = (const floatx4*)(p.x + pl * p.HW);
@@ -899,23 +688,13 @@ __global__ __launch_bounds__(256) void bn_large_apply_kernel(const FwdP p, const
     }
 }
 
+// (both backward kernels fold the drop-connect factor into gate and dpooled / HW: bn_dz with GATE, without DROP)
 template <int ACT>
-__device__ __forceinline__ floatx4 large_dz(const floatx4 xv, const floatx4 dv, float mean, float invstd, float g, float be, float gt, float dpo,
-                                            floatx4& xh) {
-    floatx4 dz;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        xh[k] = (xv[k] - mean) * invstd;
-        dz[k] = fmaf(dv[k], gt, dpo) * act_grad<ACT>(fmaf(xh[k], g, be));
-    }
-    return dz;
-}
-
-template <int ACT>
-__global__ __launch_bounds__(256) void bn_large_bwd_stats_kernel(const BwdP p, double* __restrict__ part, int S) {
+__global__ __launch_bounds__(256) void bn_large_bwd_stats_kernel(const srbh_bnact_bwd_args p, double* __restrict__ part, int S) {
     __shared__ double red[4];
     const int c = blockIdx.x, sp = blockIdx.y, t = threadIdx.x, n4 = p.HW >> 2;
-    const float mean = p.save_mean[c], invstd = p.save_invstd[c], g = p.gamma[c], be = p.beta[c], invHW = 1.f / (float)p.HW;
+    const BnNorm m{p.save_mean[c], p.save_invstd[c], p.gamma[c], p.beta[c]};
+    const float invHW = 1.f / (float)p.HW;
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll 2
     for (int b = sp; b < p.B; b += S) {
@@ -926,12 +705,9 @@ __global__ __launch_bounds__(256) void bn_large_bwd_stats_kernel(const BwdP p, d
         const floatx4* dp = (const floatx4*)(p.dy + pl * p.HW);
         for (int i = t; i < n4; i += 256) {
             floatx4 xh;
-            const floatx4 dz = large_dz<ACT>(xp[i], dp[i], mean, invstd, g, be, gt, dpo, xh);
+            const floatx4 dz = bn_dz<ACT, true, false>(xp[i], dp[i], m, gt, dpo, 1.f, xh);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                s1 += dz[k];
-                s2 = fmaf(dz[k], xh[k], s2);
-            }
+            for (int k = 0; k < 4; ++k) bn_bwd_accum(dz[k], xh[k], s1, s2);
         }
     }
     const double d1 = wg_sum_double((double)s1, red, t), d2 = wg_sum_double((double)s2, red, t);
@@ -942,7 +718,7 @@ __global__ __launch_bounds__(256) void bn_large_bwd_stats_kernel(const BwdP p, d
 }
 
 template <int ACT>
-__global__ __launch_bounds__(256) void bn_large_bwd_apply_kernel(const BwdP p, const double* __restrict__ part, int S) {
+__global__ __launch_bounds__(256) void bn_large_bwd_apply_kernel(const srbh_bnact_bwd_args p, const double* __restrict__ part, int S) {
     const long pl = blockIdx.x;
     const int c = (int)(pl % p.C), t = threadIdx.x, n4 = p.HW >> 2;
     const long b = pl / p.C;
@@ -957,8 +733,9 @@ __global__ __launch_bounds__(256) void bn_large_bwd_apply_kernel(const BwdP p, c
     }
     if (!p.dx) return;
     const double n = (double)p.B * (double)p.HW;
-    const float k1 = (float)(d1 / n), k2 = (float)(d2 / n);
-    const float mean = p.save_mean[c], invstd = p.save_invstd[c], g = p.gamma[c], be = p.beta[c], gi = g * invstd, invHW = 1.f / (float)p.HW;
+    const BnNorm m{p.save_mean[c], p.save_invstd[c], p.gamma[c], p.beta[c]};
+    const BnBwdK kk{(float)(d1 / n), (float)(d2 / n), m.g * m.invstd};       // (the sums are double partials here, not bn_bwd_sums')
+    const float invHW = 1.f / (float)p.HW;
     const float dr = p.drop ? p.drop[b] : 1.f;
     const float gt = (p.gate ? p.gate[pl] : 1.f) * dr, dpo = (p.gate ? p.dpooled[pl] * invHW : 0.f) * dr;
     const floatx4* xp = (const floatx4*)(p.x + pl * p.HW);
@@ -966,9 +743,9 @@ __global__ __launch_bounds__(256) void bn_large_bwd_apply_kernel(const BwdP p, c
     floatx4* op = (floatx4*)(p.dx + pl * p.HW);
     for (int i = t; i < n4; i += 256) {
         floatx4 xh;
-        floatx4 dz = large_dz<ACT>(xp[i], dp[i], mean, invstd, g, be, gt, dpo, xh);
+        floatx4 dz = bn_dz<ACT, true, false>(xp[i], dp[i], m, gt, dpo, 1.f, xh);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) dz[k] = gi * (dz[k] - k1 - xh[k] * k2);
+        for (int k = 0; k < 4; ++k) dz[k] = bn_dx(dz[k], xh[k], kk);
         op[i] = dz;
     }
 }
@@ -986,15 +763,33 @@ int se_chunks(int C) {                      // channel chunks of the squeeze-exc
     return n < 1 ? 1 : (n > 16 ? ((C + 1023) / 1024 > 16 ? (C + 1023) / 1024 : 16) : n);
 }
 int row_width(int HW) { return HW == 256 ? 256 : ((HW == 64 || HW == 16 || HW == 4 || HW == 1) ? 64 : 0); }
+int mid_logw(int H, int W) { return (H == W && (W == 2 || W == 4 || W == 8)) ? (W == 2 ? 1 : W == 4 ? 2 : 3) : -1; }
 size_t fwd_lds(int B, int RW) { return (size_t)B * RW * 4; }
-}  // namespace
 
-static int mid_logw(int H, int W) { return (H == W && (W == 2 || W == 4 || W == 8)) ? (W == 2 ? 1 : W == 4 ? 2 : 3) : -1; }
+// One launch of an LDS-resident kernel (64 * NW threads, `lds` bytes of dynamic LDS, its arguments by value); the kernel's dynamic-LDS limit is
+// raised to `cap` first, once per device and kernel form.
+template <auto Kernel, class... Args>
+int launch_resident(dim3 grid, size_t lds, int cap, void* stream, const Args&... args) {
+    SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, cap)));
+    hipLaunchKernelGGL(Kernel, grid, dim3(64 * NW), lds, (hipStream_t)stream, args...);
+    SRBH_HIP(hipGetLastError());
+    return SRBH_OK;
+}
+// act (0 | 1 | 2) -> f(integral_constant ACT); act and the row width (64 | 256) -> f(ACT, VEC); the depthwise kernel size (3 | 5) -> f(K)
+template <class F>
+int with_act(int act, F&& f) { return with_const<3>(act, f); }
+template <class F>
+int with_act_vec(int act, int RW, F&& f) {
+    return with_act(act, [&](auto A) { return RW == 256 ? f(A, std::integral_constant<int, 4>{}) : f(A, std::integral_constant<int, 1>{}); });
+}
+template <class F>
+int with_k(int K, F&& f) { return K == 3 ? f(std::integral_constant<int, 3>{}) : f(std::integral_constant<int, 5>{}); }
+}  // namespace
 
 /* 1 when the fused MBConv middle kernels take the shape: square planes of 2x2, 4x4 or 8x8, depthwise kernel 3 or 5 with stride 1, and
  * three copies of the workgroup's B x 64-float run within LDS */
 extern "C" int srbh_mbconv_mid_supported(int B, int C, int H, int W, int K, int stride) {
-    return B > 0 && C > 0 && mid_logw(H, W) > 0 && (K == 3 || K == 5) && stride == 1 && (size_t)3 * B * 64 * 4 <= (size_t)MAX_LDS_B - 32 * 1024;
+    return B > 0 && C > 0 && mid_logw(H, W) > 0 && (K == 3 || K == 5) && stride == 1 && (size_t)3 * B * 64 * 4 <= (size_t)MID_LDS_CAP;
 }
 
 extern "C" int srbh_mbconv_mid_fwd(const srbh_mbmid_args* a, void* stream) {
@@ -1002,25 +797,10 @@ extern "C" int srbh_mbconv_mid_fwd(const srbh_mbmid_args* a, void* stream) {
                  a->running_mean1 && a->running_var1 && a->mean0 && a->invstd0 && a->mean1 && a->invstd1 && a->d_pre && a->y && a->pooled,
                  "srbh_mbconv_mid_fwd: null pointer");
     SRBH_REQUIRE(srbh_mbconv_mid_supported(a->B, a->C, a->H, a->W, a->K, 1), "srbh_mbconv_mid_fwd: unsupported shape B=%d C=%d %dx%d k%d", a->B, a->C, a->H, a->W, a->K);
-    MidFwdP p;
-    p.e_pre = a->e_pre; p.wdw = a->wdw;
-    p.g0 = a->gamma0; p.b0 = a->beta0; p.rm0 = a->running_mean0; p.rv0 = a->running_var0; p.mean0 = a->mean0; p.invstd0 = a->invstd0;
-    p.g1 = a->gamma1; p.b1 = a->beta1; p.rm1 = a->running_mean1; p.rv1 = a->running_var1; p.mean1 = a->mean1; p.invstd1 = a->invstd1;
-    p.d_pre = a->d_pre; p.y = a->y; p.pooled = a->pooled;
-    p.mom0 = a->momentum0; p.eps0 = a->eps0; p.mom1 = a->momentum1; p.eps1 = a->eps1;
-    p.B = a->B; p.C = a->C; p.HW = a->H * a->W; p.logw = mid_logw(a->H, a->W);
-    const int cpw = 64 / p.HW;
-    const size_t lds = (size_t)2 * p.B * 64 * 4;
-    const dim3 grid((p.C + cpw - 1) / cpw);
-    if (a->K == 3) {
-        SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)mbconv_mid_fwd_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS_B - 32 * 1024)));
-        hipLaunchKernelGGL(mbconv_mid_fwd_kernel<3>, grid, dim3(64 * NW), lds, (hipStream_t)stream, p);
-    } else {
-        SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)mbconv_mid_fwd_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS_B - 32 * 1024)));
-        hipLaunchKernelGGL(mbconv_mid_fwd_kernel<5>, grid, dim3(64 * NW), lds, (hipStream_t)stream, p);
-    }
-    SRBH_HIP(hipGetLastError());
-    return SRBH_OK;
+    const int HW = a->H * a->W, cpw = 64 / HW;
+    return with_k(a->K, [&](auto K) {
+        return launch_resident<mbconv_mid_fwd_kernel<K>>(dim3((a->C + cpw - 1) / cpw), (size_t)2 * a->B * 64 * 4, MID_LDS_CAP, stream, *a, HW, mid_logw(a->H, a->W));
+    });
 }
 
 extern "C" int srbh_mbconv_mid_bwd(const srbh_mbmid_bwd_args* a, void* stream) {
@@ -1028,24 +808,10 @@ extern "C" int srbh_mbconv_mid_bwd(const srbh_mbmid_bwd_args* a, void* stream) {
                  a->gamma1 && a->beta1 && a->mean1 && a->invstd1 && a->dwdw && a->dgamma0 && a->dbeta0 && a->dgamma1 && a->dbeta1,
                  "srbh_mbconv_mid_bwd: null pointer");
     SRBH_REQUIRE(srbh_mbconv_mid_supported(a->B, a->C, a->H, a->W, a->K, 1), "srbh_mbconv_mid_bwd: unsupported shape B=%d C=%d %dx%d k%d", a->B, a->C, a->H, a->W, a->K);
-    MidBwdP p;
-    p.dout = a->dout; p.gate = a->gate; p.dpooled = a->dpooled; p.d_pre = a->d_pre; p.e_pre = a->e_pre; p.wdw = a->wdw;
-    p.g0 = a->gamma0; p.b0 = a->beta0; p.mean0 = a->mean0; p.invstd0 = a->invstd0;
-    p.g1 = a->gamma1; p.b1 = a->beta1; p.mean1 = a->mean1; p.invstd1 = a->invstd1;
-    p.de_pre = a->de_pre; p.dwdw = a->dwdw; p.dg0 = a->dgamma0; p.db0 = a->dbeta0; p.dg1 = a->dgamma1; p.db1 = a->dbeta1;
-    p.B = a->B; p.C = a->C; p.HW = a->H * a->W; p.logw = mid_logw(a->H, a->W);
-    const int cpw = 64 / p.HW;
-    const size_t lds = (size_t)3 * p.B * 64 * 4;
-    const dim3 grid((p.C + cpw - 1) / cpw);
-    if (a->K == 3) {
-        SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)mbconv_mid_bwd_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS_B - 32 * 1024)));
-        hipLaunchKernelGGL(mbconv_mid_bwd_kernel<3>, grid, dim3(64 * NW), lds, (hipStream_t)stream, p);
-    } else {
-        SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)mbconv_mid_bwd_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS_B - 32 * 1024)));
-        hipLaunchKernelGGL(mbconv_mid_bwd_kernel<5>, grid, dim3(64 * NW), lds, (hipStream_t)stream, p);
-    }
-    SRBH_HIP(hipGetLastError());
-    return SRBH_OK;
+    const int HW = a->H * a->W, cpw = 64 / HW;
+    return with_k(a->K, [&](auto K) {
+        return launch_resident<mbconv_mid_bwd_kernel<K>>(dim3((a->C + cpw - 1) / cpw), (size_t)3 * a->B * 64 * 4, MID_LDS_CAP, stream, *a, HW, mid_logw(a->H, a->W));
+    });
 }
 
 extern "C" int srbh_bn_act_train_supported(int B, int C, int HW) {
@@ -1063,42 +829,21 @@ extern "C" int srbh_bn_act_train_fwd(const srbh_bnact_args* a, void* stream) {
     SRBH_REQUIRE(a->act >= 0 && a->act <= 2, "srbh_bn_act_train_fwd: act must be 0 (none), 1 (SiLU) or 2 (ReLU)");
     SRBH_REQUIRE(srbh_bn_act_train_supported(a->B, a->C, a->HW), "srbh_bn_act_train_fwd: unsupported shape B=%d C=%d HW=%d (planes of 1, 4, 16, 64 or 256 floats with B * row within LDS, or a multiple of 4 from 256 up)", a->B, a->C, a->HW);
     SRBH_REQUIRE((a->running_mean == nullptr) == (a->running_var == nullptr), "srbh_bn_act_train_fwd: running_mean / running_var go together");
-    FwdP p;
-    p.x = a->x; p.y = a->y; p.gamma = a->gamma; p.beta = a->beta; p.running_mean = a->running_mean; p.running_var = a->running_var;
-    p.save_mean = a->save_mean; p.save_invstd = a->save_invstd; p.pooled = a->pooled; p.res = a->res; p.drop = a->drop;
-    p.momentum = a->momentum; p.eps = a->eps; p.B = a->B; p.C = a->C; p.HW = a->HW;
     if (srbh_bn_act_train_supported(a->B, a->C, a->HW) == 2) {
         SRBH_REQUIRE(a->ws, "srbh_bn_act_train_fwd: planes of %d elements need the workspace (srbh_bn_act_train_ws_bytes)", a->HW);
-        const int S = large_splits(p.B, p.C);
+        const int S = large_splits(a->B, a->C);
         double* part = (double*)a->ws;
-        hipLaunchKernelGGL(bn_large_stats_kernel, dim3(p.C, S), dim3(256), 0, (hipStream_t)stream, p.x, part, p.B, p.C, p.HW, S);
-        const dim3 gp((unsigned)((long)p.B * p.C));
-        if (a->act == 0) hipLaunchKernelGGL(bn_large_apply_kernel<0>, gp, dim3(256), 0, (hipStream_t)stream, p, part, S);
-        else if (a->act == 1) hipLaunchKernelGGL(bn_large_apply_kernel<1>, gp, dim3(256), 0, (hipStream_t)stream, p, part, S);
-        else hipLaunchKernelGGL(bn_large_apply_kernel<2>, gp, dim3(256), 0, (hipStream_t)stream, p, part, S);
-        SRBH_HIP(hipGetLastError());
-        return SRBH_OK;
+        hipLaunchKernelGGL(bn_large_stats_kernel, dim3(a->C, S), dim3(256), 0, (hipStream_t)stream, a->x, part, a->B, a->C, a->HW, S);
+        return with_act(a->act, [&](auto A) {
+            hipLaunchKernelGGL(bn_large_apply_kernel<A>, dim3((unsigned)((long)a->B * a->C)), dim3(256), 0, (hipStream_t)stream, *a, part, S);
+            SRBH_HIP(hipGetLastError());
+            return SRBH_OK;
+        });
     }
-    const int RW = row_width(a->HW), cpw = RW / p.HW;
-    const size_t lds = fwd_lds(p.B, RW);
-    const dim3 grid((p.C + cpw - 1) / cpw);
-#define SRBH_FWD(A_, V_)                                                                                                                  \
-    do {                                                                                                                                  \
-        SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)bn_act_train_fwd_kernel<A_, V_>, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS_B))); \
-        hipLaunchKernelGGL((bn_act_train_fwd_kernel<A_, V_>), grid, dim3(64 * NW), lds, (hipStream_t)stream, p);                              \
-    } while (0)
-#define SRBH_FWD_V(A_)          \
-    do {                        \
-        if (RW == 256) SRBH_FWD(A_, 4); \
-        else SRBH_FWD(A_, 1);   \
-    } while (0)
-    if (a->act == 0) SRBH_FWD_V(0);
-    else if (a->act == 1) SRBH_FWD_V(1);
-    else SRBH_FWD_V(2);
-#undef SRBH_FWD_V
-#undef SRBH_FWD
-    SRBH_HIP(hipGetLastError());
-    return SRBH_OK;
+    const int RW = row_width(a->HW), cpw = RW / a->HW;
+    return with_act_vec(a->act, RW, [&](auto A, auto V) {
+        return launch_resident<bn_act_train_fwd_kernel<A, V>>(dim3((a->C + cpw - 1) / cpw), fwd_lds(a->B, RW), MAX_LDS_B, stream, *a);
+    });
 }
 
 extern "C" int srbh_bn_act_train_bwd(const srbh_bnact_bwd_args* a, void* stream) {
@@ -1107,48 +852,21 @@ extern "C" int srbh_bn_act_train_bwd(const srbh_bnact_bwd_args* a, void* stream)
     SRBH_REQUIRE(a->act >= 0 && a->act <= 2, "srbh_bn_act_train_bwd: act must be 0 (none), 1 (SiLU) or 2 (ReLU)");
     SRBH_REQUIRE(srbh_bn_act_train_supported(a->B, a->C, a->HW), "srbh_bn_act_train_bwd: unsupported shape B=%d C=%d HW=%d", a->B, a->C, a->HW);
     SRBH_REQUIRE((a->gate == nullptr) == (a->dpooled == nullptr), "srbh_bn_act_train_bwd: gate / dpooled go together");
-    BwdP p;
-    p.dy = a->dy; p.x = a->x; p.gamma = a->gamma; p.beta = a->beta; p.save_mean = a->save_mean; p.save_invstd = a->save_invstd;
-    p.gate = a->gate; p.dpooled = a->dpooled; p.drop = a->drop; p.dx = a->dx; p.dgamma = a->dgamma; p.dbeta = a->dbeta;
-    p.B = a->B; p.C = a->C; p.HW = a->HW;
     if (srbh_bn_act_train_supported(a->B, a->C, a->HW) == 2) {
         SRBH_REQUIRE(a->ws, "srbh_bn_act_train_bwd: planes of %d elements need the workspace (srbh_bn_act_train_ws_bytes)", a->HW);
-        const int S = large_splits(p.B, p.C);
+        const int S = large_splits(a->B, a->C);
         double* part = (double*)a->ws;
-        const dim3 gs(p.C, S), gp((unsigned)((long)p.B * p.C));
-        if (a->act == 0) {
-            hipLaunchKernelGGL(bn_large_bwd_stats_kernel<0>, gs, dim3(256), 0, (hipStream_t)stream, p, part, S);
-            hipLaunchKernelGGL(bn_large_bwd_apply_kernel<0>, gp, dim3(256), 0, (hipStream_t)stream, p, part, S);
-        } else if (a->act == 1) {
-            hipLaunchKernelGGL(bn_large_bwd_stats_kernel<1>, gs, dim3(256), 0, (hipStream_t)stream, p, part, S);
-            hipLaunchKernelGGL(bn_large_bwd_apply_kernel<1>, gp, dim3(256), 0, (hipStream_t)stream, p, part, S);
-        } else {
-            hipLaunchKernelGGL(bn_large_bwd_stats_kernel<2>, gs, dim3(256), 0, (hipStream_t)stream, p, part, S);
-            hipLaunchKernelGGL(bn_large_bwd_apply_kernel<2>, gp, dim3(256), 0, (hipStream_t)stream, p, part, S);
-        }
-        SRBH_HIP(hipGetLastError());
-        return SRBH_OK;
+        return with_act(a->act, [&](auto A) {
+            hipLaunchKernelGGL(bn_large_bwd_stats_kernel<A>, dim3(a->C, S), dim3(256), 0, (hipStream_t)stream, *a, part, S);
+            hipLaunchKernelGGL(bn_large_bwd_apply_kernel<A>, dim3((unsigned)((long)a->B * a->C)), dim3(256), 0, (hipStream_t)stream, *a, part, S);
+            SRBH_HIP(hipGetLastError());
+            return SRBH_OK;
+        });
     }
-    const int RW = row_width(a->HW), cpw = RW / p.HW;
-    const size_t lds = 2 * fwd_lds(p.B, RW);
-    const dim3 grid((p.C + cpw - 1) / cpw);
-#define SRBH_BWD(A_, V_)                                                                                                                  \
-    do {                                                                                                                                  \
-        SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)bn_act_train_bwd_kernel<A_, V_>, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS_B))); \
-        hipLaunchKernelGGL((bn_act_train_bwd_kernel<A_, V_>), grid, dim3(64 * NW), lds, (hipStream_t)stream, p);                              \
-    } while (0)
-#define SRBH_BWD_V(A_)          \
-    do {                        \
-        if (RW == 256) SRBH_BWD(A_, 4); \
-        else SRBH_BWD(A_, 1);   \
-    } while (0)
-    if (a->act == 0) SRBH_BWD_V(0);
-    else if (a->act == 1) SRBH_BWD_V(1);
-    else SRBH_BWD_V(2);
-#undef SRBH_BWD_V
-#undef SRBH_BWD
-    SRBH_HIP(hipGetLastError());
-    return SRBH_OK;
+    const int RW = row_width(a->HW), cpw = RW / a->HW;
+    return with_act_vec(a->act, RW, [&](auto A, auto V) {
+        return launch_resident<bn_act_train_bwd_kernel<A, V>>(dim3((a->C + cpw - 1) / cpw), 2 * fwd_lds(a->B, RW), MAX_LDS_B, stream, *a);
+    });
 }
 
 extern "C" int srbh_se_train_fwd(float* y, const float* pooled, const float* w1, const float* b1, const float* w2, const float* b2,
@@ -1185,9 +903,10 @@ extern "C" int srbh_se_train_bwd(const float* dout, const float* x, const float*
     const long waves = HW < 64 ? (planes * HW + 63) / 64 : planes;
     const dim3 g1((unsigned)((waves + 3) / 4));
     SRBH_REQUIRE(HW >= 64 || (HW & (HW - 1)) == 0, "srbh_se_train_bwd: planes below 64 elements must be a power of two (HW = %d)", HW);
-    if (act == 0) hipLaunchKernelGGL(se_bwd_dgate_kernel<0>, g1, dim3(256), 0, (hipStream_t)stream, dout, x, gamma, beta, save_mean, save_invstd, draw, planes, C, HW);
-    else if (act == 1) hipLaunchKernelGGL(se_bwd_dgate_kernel<1>, g1, dim3(256), 0, (hipStream_t)stream, dout, x, gamma, beta, save_mean, save_invstd, draw, planes, C, HW);
-    else hipLaunchKernelGGL(se_bwd_dgate_kernel<2>, g1, dim3(256), 0, (hipStream_t)stream, dout, x, gamma, beta, save_mean, save_invstd, draw, planes, C, HW);
+    with_act(act, [&](auto A) {
+        hipLaunchKernelGGL(se_bwd_dgate_kernel<A>, g1, dim3(256), 0, (hipStream_t)stream, dout, x, gamma, beta, save_mean, save_invstd, draw, planes, C, HW);
+        return SRBH_OK;
+    });
     hipLaunchKernelGGL(se_bwd_expand_kernel, dim3(B, nch), dim3(256), 0, (hipStream_t)stream, draw, gate, w2, dsig, part, C, SQ, CC);
     hipLaunchKernelGGL(se_bwd_reduce_kernel, dim3(B, nch), dim3(256), 0, (hipStream_t)stream, part, hidden_pre, w1, dhp, dpooled, C, SQ, CC);
     GemmTN ga, gb;                 // dw2 [C][SQ] = dsig^T hidden (+ db2);  dw1 [SQ][C] = dhp^T pooled (+ db1)

@@ -87,7 +87,8 @@ def test_bn_act_train_large_channel_offset(B, C, H):
     assert rel(y, yr) <= 20 * TOL          # (x itself carries 100 * 2^-24 = 6e-6 of rounding relative to its unit spread)
 
 
-@pytest.mark.parametrize("B,C,SQ,H", [(6, 144, 6, 16), (64, 40, 10, 8), (5, 672, 28, 4), (3, 2688, 112, 2), (2, 19, 3, 2), (4, 24, 6, 32)])
+@pytest.mark.parametrize("B,C,SQ,H", [(6, 144, 6, 16), (64, 40, 10, 8), (5, 672, 28, 4), (3, 2688, 112, 2), (2, 19, 3, 2), (4, 24, 6, 32),
+                                      (70, 19, 3, 2), (66, 8, 4, 16)])     # (B > 64 with gate + dpooled: a second round of the backward's batched loads)
 def test_bn_swish_se_train_matches_stock_ops(B, C, SQ, H):
     from srbh_amd import mbconv_autograd as MB
     g = torch.Generator().manual_seed(B * 1000 + C + H)
@@ -243,7 +244,8 @@ def test_transpose_many_and_encoder_refresh():
     assert torch.equal(c.__dict__["_srbh_wt"], c.weight.detach().view(c.weight.shape[0], -1).t())
 
 
-@pytest.mark.parametrize("B,inp,H,K", [(64, 28, 4, 3), (7, 40, 4, 5), (64, 68, 2, 5), (5, 20, 8, 3), (33, 14, 8, 5), (3, 112, 2, 3)])
+@pytest.mark.parametrize("B,inp,H,K", [(64, 28, 4, 3), (7, 40, 4, 5), (64, 68, 2, 5), (5, 20, 8, 3), (33, 14, 8, 5), (3, 112, 2, 3),
+                                       (70, 6, 2, 5), (70, 6, 8, 3)])      # (B > 64: a second round of the kernels' batched loads)
 def test_fused_mbconv_middle_equals_the_separate_kernels(B, inp, H, K, monkeypatch):
     """srbh_mbconv_mid_fwd / _bwd (round 4): BatchNorm0 + SiLU -> depthwise -> BatchNorm1 + SiLU + pool of an MBConv block as ONE launch per
     direction, against the same block on the separate kernels (bn_act, depthwise, bn_act + pool: each already pinned against the stock
