@@ -758,6 +758,28 @@ int srbh_height_metric_sums(const float* pred, const float* ref, const long long
 int srbh_confusion_add(const long long* pred, const long long* label, long n, int num_class,
                        unsigned long long* cm, int* bad_flag, void* stream);
 
+/* ---- SR-stage quality metrics as one-read reductions (reference SR/psnr_ssim.py; csrc/srbh_sr_metrics.hip) ---------------------------
+ * a, b: fp32 images of logical shape (B, C, H, W), C = 1 | 3, each with its own four ELEMENT strides {batch, channel, row, column} (host
+ * array; non-negative): a channels_last network output, an NCHW target and a cropped view are all read in place.  y_only (C == 3): the
+ * value used is the BT.601 luma of rgb2ycbcr_pt (psnr_ssim.py:122-144), computed in fp32 as there; the effective channel count Ce is then 1,
+ * otherwise Ce = C.  Everything behind the fp32 values is float64.  Results are OVERWRITTEN (not accumulated) and bit-reproducible: an image's
+ * numbers depend neither on the run nor on the batch it travels in (per-workgroup partial sums in fixed slots of `ws`, folded in a fixed
+ * order; no floating-point atomics).  ws: srbh_*_ws_bytes bytes of device memory, no initialisation needed.  One launch + one small fold.
+ *
+ * srbh_sr_psnr_ssim_sums: per image i,  sq[i] = sum (a - b)^2 over Ce x H x W (calculate_psnr_pt :228-231 takes its mean), and
+ *   ssim[i] = sum of the SSIM map over Ce x (H-10) x (W-10) (_ssim_pth :352-382: 11-tap Gaussian sigma 1.5, inputs * 255, C1 = (0.01*255)^2,
+ *   C2 = (0.03*255)^2; run as a separable horizontal + vertical pass).  Either of sq / ssim may be NULL; with ssim NULL no window pass runs
+ *   and H, W < 11 are allowed.
+ * srbh_sr_cpsnr_sums: for calculate_cpsnr_pt (:443-490).  sd / sqd [B][Ce][81]: for offset index ro * 9 + co (ro, co in 0..8), the sums of
+ *   d and d^2 over the (H-8) x (W-8) window, d = a[r+ro, c+co] - b[r+8-ro, c+8-co] (:473-476).  The bias-corrected MSE of :479-484 over a set
+ *   of images is  sum_c [S(d^2) - S(d)^2 / N] / (Ce N)  with S the sums over the set and N its element count per channel. */
+size_t srbh_sr_psnr_ssim_ws_bytes(int B, int H, int W);
+int srbh_sr_psnr_ssim_sums(const float* a, const long* a_strides, const float* b, const long* b_strides, int B, int C, int H, int W,
+                           int y_only, double* sq, double* ssim, void* ws, void* stream);
+size_t srbh_sr_cpsnr_ws_bytes(int B, int C, int H, int W, int y_only);
+int srbh_sr_cpsnr_sums(const float* a, const long* a_strides, const float* b, const long* b_strides, int B, int C, int H, int W,
+                       int y_only, double* sd, double* sqd, void* ws, void* stream);
+
 /* ---- The middle of an MBConv block in ONE launch per direction (round 4; efficientnet_pytorch MBConvBlock.forward between the expand and
  * the project conv, run by smp's encoder at mymodels.py:276): BatchNorm0 (training) + SiLU -> depthwise KxK, stride 1, "same" zero padding ->
  * BatchNorm1 (training) + SiLU (+ the plane means squeeze-and-excitation pools).  fp32 NCHW, square planes 2x2 / 4x4 / 8x8, K = 3 | 5.

@@ -17,7 +17,7 @@ CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(ROOT, "include")
 LIB_PATH = os.path.join(_HERE, "libsrbh.so")
 _DEV_LIB = os.environ.get("SRBH_LIB_PATH")      # developer A/B only (tools/ab_variants.sh): load another build of the same ABI
-SOURCES = ["srbh_conv3x3.hip", "srbh_aux.hip", "srbh_rrdbnet.hip", "srbh_ptrunk.hip", "srbh_trunk_wgrad.hip", "srbh_ptail.hip", "srbh_ptail_split.hip", "srbh_head.hip", "srbh_head_bwd.hip", "srbh_mosaic.hip", "srbh_loader.hip", "srbh_loss.hip", "srbh_dwconv.hip", "srbh_mbconv.hip", "srbh_pwconv.hip", "srbh_dconv.hip", "srbh_optim.hip"]
+SOURCES = ["srbh_conv3x3.hip", "srbh_aux.hip", "srbh_rrdbnet.hip", "srbh_ptrunk.hip", "srbh_trunk_wgrad.hip", "srbh_ptail.hip", "srbh_ptail_split.hip", "srbh_head.hip", "srbh_head_bwd.hip", "srbh_mosaic.hip", "srbh_loader.hip", "srbh_loss.hip", "srbh_sr_metrics.hip", "srbh_dwconv.hip", "srbh_mbconv.hip", "srbh_pwconv.hip", "srbh_dconv.hip", "srbh_optim.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # NOTE: `-mllvm -amdgpu-mfma-vgpr-form=1` (accumulators in VGPRs: no v_accvgpr copies at K-loop back-edges).  Round 1 saw the
 # first persistent trunk kernel produce non-deterministic garbage with it; round 3 re-ran it on the current kernel (ptrunk3:
@@ -322,6 +322,10 @@ SIGNATURES = {
     "srbh_cedice_grad": (_i, [_vp, _i, _i, C.c_long, C.c_long, C.c_long, C.c_long, _vp, _vp, _vp, _vp, _vp]),
     "srbh_height_metric_sums": (_i, [_vp, _vp, _vp, C.c_long, _i, _vp, _vp]),
     "srbh_confusion_add": (_i, [_vp, _vp, C.c_long, _i, _vp, _vp, _vp]),
+    "srbh_sr_psnr_ssim_ws_bytes": (_sz, [_i, _i, _i]),
+    "srbh_sr_psnr_ssim_sums": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "srbh_sr_cpsnr_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "srbh_sr_cpsnr_sums": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "srbh_trunk_timing": (_i, [_i]),
     "srbh_trunk_last_ms": (_i, [C.POINTER(C.c_float)]),
     "srbh_trunk_kernel_name": (C.c_char_p, []),

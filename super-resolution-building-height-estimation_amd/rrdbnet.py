@@ -702,3 +702,16 @@ class RealESRGAN:
     @torch.no_grad()
     def predict(self, lr):
         return self.net_g(lr.to(self.device))
+
+    @torch.no_grad()
+    def validate(self, pairs, crop_border=0, test_y_channel=False):
+        """Score the generator on an iterable of ``(lq, gt)`` batches with the reference's SR metrics (SR/psnr_ssim.py; sr_metrics.py):
+        ``predict`` each batch, feed ``sr_metrics.SRQuality``.  Returns {"psnr", "ssim", "cpsnr", "count"} -- per-image values averaged over
+        the images -- as Python numbers; the only host synchronisation is the one read at the end."""
+        from .sr_metrics import SRQuality
+        quality = SRQuality(crop_border=crop_border, test_y_channel=test_y_channel, device=self.device)
+        for lq, gt in pairs:
+            quality.addBatch(self.predict(lq), gt.to(self.device, non_blocking=True))
+        res = quality.result()
+        psnr, ssim, cpsnr = torch.stack([res["psnr"], res["ssim"], res["cpsnr"]]).tolist()
+        return {"psnr": psnr, "ssim": ssim, "cpsnr": cpsnr, "count": res["count"]}
