@@ -780,6 +780,35 @@ size_t srbh_sr_cpsnr_ws_bytes(int B, int C, int H, int W, int y_only);
 int srbh_sr_cpsnr_sums(const float* a, const long* a_strides, const float* b, const long* b_strides, int B, int C, int H, int W,
                        int y_only, double* sd, double* sqd, void* ws, void* stream);
 
+/* ---- Height-stage validation / test pass as one read of a batch (reference train.py:315-344 vtest_epoch, :427-486 vtest_epoch2,
+ * metrics.py:67-74 genConfusionMatrix, :186-200 HeightMetric.addBatch; csrc/srbh_eval.hip) ---------------------------------------------
+ * height fp32 (B, HW) with a batch ELEMENT stride (the model's (B,1,H,W) output, or a batch slice of it, is read in place); logits fp32
+ * (B, C, HW) with batch / channel / pixel element strides as for srbh_cedice_sums (NCHW and channels_last are both read in place),
+ * 2 <= C <= 16; ref fp32 (B, HW) and label (B, HW), int64 or (label_u8 != 0) uint8, both contiguous.  Per image b, OVERWRITTEN:
+ *   sums[b][k][4] = { sum d^2, sum |d|, sum d, count } over the pixels with label k, d = (double)height - (double)ref (metrics.py:186-200
+ *                   forms rmse / mae / me per class from exactly these; train.py:333-336, :444 take sqrt(mean d^2) over all pixels);
+ *   cm[b][label * C + pred] = pixel counts, pred = argmax of the C logits as torch.argmax (train.py:446) takes it: the first index among
+ *                   equal maxima, a NaN counts as the maximum and the first NaN wins (metrics.py:71-73).
+ * *bad |= 1 if a label lies outside [0, C) (sticky: zeroed by the caller once, never cleared here); such a pixel is counted nowhere.
+ * Optional (NULL: not produced) maps of every pixel, (B, HW) contiguous: q_height = np.round(max(height, 0) * 10) as uint16, half to even
+ * (train.py:464-466), cls_map = the argmax as uint8 (train.py:476).
+ * Bit-reproducible: the pixel -> workgroup map and every summation order depend on HW only (float64 partial sums in registers, one slot of
+ * `ws` per workgroup, an ordered fold; no floating-point atomics), so an image's numbers depend neither on the run, nor on the batch it
+ * travels in, nor on the logits layout.  ws: at least srbh_eval_ws_bytes(B, HW, C) bytes of device memory (0 for arguments the call would
+ * refuse), no initialisation needed.  One launch + one small fold. */
+typedef struct srbh_eval_args {
+    const float* height; long height_bs;
+    const float* logits; long logits_bs, logits_cs, logits_ps;
+    const float* ref;
+    const void* label; int label_u8;
+    int B, C, HW;
+    double* sums; long long* cm; int* bad;
+    unsigned short* q_height; unsigned char* cls_map;
+    void* ws; size_t ws_bytes;
+} srbh_eval_args;
+size_t srbh_eval_ws_bytes(int B, int HW, int C);
+int srbh_eval_sums(const srbh_eval_args* a, void* stream);
+
 /* ---- The middle of an MBConv block in ONE launch per direction (round 4; efficientnet_pytorch MBConvBlock.forward between the expand and
  * the project conv, run by smp's encoder at mymodels.py:276): BatchNorm0 (training) + SiLU -> depthwise KxK, stride 1, "same" zero padding ->
  * BatchNorm1 (training) + SiLU (+ the plane means squeeze-and-excitation pools).  fp32 NCHW, square planes 2x2 / 4x4 / 8x8, K = 3 | 5.

@@ -17,7 +17,7 @@ CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(ROOT, "include")
 LIB_PATH = os.path.join(_HERE, "libsrbh.so")
 _DEV_LIB = os.environ.get("SRBH_LIB_PATH")      # developer A/B only (tools/ab_variants.sh): load another build of the same ABI
-SOURCES = ["srbh_conv3x3.hip", "srbh_aux.hip", "srbh_rrdbnet.hip", "srbh_ptrunk.hip", "srbh_trunk_wgrad.hip", "srbh_ptail.hip", "srbh_ptail_split.hip", "srbh_head.hip", "srbh_head_bwd.hip", "srbh_mosaic.hip", "srbh_loader.hip", "srbh_loss.hip", "srbh_sr_metrics.hip", "srbh_dwconv.hip", "srbh_mbconv.hip", "srbh_pwconv.hip", "srbh_dconv.hip", "srbh_optim.hip"]
+SOURCES = ["srbh_conv3x3.hip", "srbh_aux.hip", "srbh_rrdbnet.hip", "srbh_ptrunk.hip", "srbh_trunk_wgrad.hip", "srbh_ptail.hip", "srbh_ptail_split.hip", "srbh_head.hip", "srbh_head_bwd.hip", "srbh_mosaic.hip", "srbh_loader.hip", "srbh_loss.hip", "srbh_sr_metrics.hip", "srbh_eval.hip", "srbh_dwconv.hip", "srbh_mbconv.hip", "srbh_pwconv.hip", "srbh_dconv.hip", "srbh_optim.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # NOTE: `-mllvm -amdgpu-mfma-vgpr-form=1` (accumulators in VGPRs: no v_accvgpr copies at K-loop back-edges).  Round 1 saw the
 # first persistent trunk kernel produce non-deterministic garbage with it; round 3 re-ran it on the current kernel (ptrunk3:
@@ -188,6 +188,16 @@ class ConvSplit(C.Structure):
     ]
 
 
+class EvalArgs(C.Structure):
+    _fields_ = [("height", C.c_void_p), ("height_bs", C.c_long),
+                ("logits", C.c_void_p), ("logits_bs", C.c_long), ("logits_cs", C.c_long), ("logits_ps", C.c_long),
+                ("ref", C.c_void_p), ("label", C.c_void_p), ("label_u8", C.c_int),
+                ("B", C.c_int), ("C", C.c_int), ("HW", C.c_int),
+                ("sums", C.c_void_p), ("cm", C.c_void_p), ("bad", C.c_void_p),
+                ("q_height", C.c_void_p), ("cls_map", C.c_void_p),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
+
+
 # every exported symbol of include/srbh.h: name -> (restype, argtypes)
 _vp, _i, _sz, _f = C.c_void_p, C.c_int, C.c_size_t, C.c_float
 SIGNATURES = {
@@ -326,6 +336,8 @@ SIGNATURES = {
     "srbh_sr_psnr_ssim_sums": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "srbh_sr_cpsnr_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "srbh_sr_cpsnr_sums": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "srbh_eval_ws_bytes": (_sz, [_i, _i, _i]),
+    "srbh_eval_sums": (_i, [C.POINTER(EvalArgs), _vp]),
     "srbh_trunk_timing": (_i, [_i]),
     "srbh_trunk_last_ms": (_i, [C.POINTER(C.c_float)]),
     "srbh_trunk_kernel_name": (C.c_char_p, []),

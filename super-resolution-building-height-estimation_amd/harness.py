@@ -826,3 +826,47 @@ def predict_tiles(net_hr, model, tiles, posall, mosaic, batch=32, rank=0, world=
         # NaN-poisoned the features; this raises with the reason instead of shipping a NaN mosaic
         net_hr.check_status()
     return hi - lo
+
+
+@torch.no_grad()
+def evaluate_tiles(net_hr, model, tiles, height_ref, build_label, batch=32, num_class=7, ref_batch=1, rank=0, world=1, keep_maps=False):
+    """The validation / test loops of the reference (train.py:315-344 vtest_epoch, :427-486 vtest_epoch2) for this rank's shard of a tile
+    set, with predict_tiles' batching and an evaluation in the place of the mosaic: RRDBNet feature extraction -> height / building
+    heads -> evaluate.HeightEvaluation.add (one reduction launch per batch, no host synchronisation).  ``tiles`` (N,8,64,64) fp32,
+    ``height_ref`` (N,256,256) fp32, ``build_label`` (N,256,256) int64 or uint8.  Full batches replay predict_tiles' captured graph (the
+    same cache entry on ``model``: validating and later predicting share one graph); the ragged tail runs as one zero-padded batch of which
+    only the real images are added.  ``ref_batch``: the reference loader's batch_size whose numbers ``result()`` should reproduce (1 in
+    main_test).  Returns the HeightEvaluation -- with keep_maps its ``maps`` lists the (uint16 height, uint8 class) rasters of every batch;
+    for world > 1 it holds this rank's images: gather and ``merge_`` in rank order."""
+    from .evaluate import HeightEvaluation
+    model.eval()
+    net_hr.eval()
+    lo, hi = shard_range(tiles.shape[0], rank, world)
+    dev = next(model.parameters()).device
+    ev = HeightEvaluation(num_class=num_class, device=dev, ref_batch=ref_batch, keep_maps=keep_maps)
+    pg = None
+    if PREDICT_GRAPH and dev.type == "cuda" and hi - lo >= batch and hasattr(net_hr, "forward_feature"):
+        pg = model.__dict__.get("_srbh_predict_graph")
+        if pg is None or pg.key != _PredictGraph.weights_key(net_hr, model, batch, dev):
+            pg = model.__dict__["_srbh_predict_graph"] = None      # (drop the old graph's memory pool first)
+            pg = model.__dict__["_srbh_predict_graph"] = _PredictGraph(net_hr, model, batch, dev, tiles.shape[1])
+    if pg is not None:
+        pg.reset()
+    for s in range(lo, hi, batch):
+        e = min(s + batch, hi)
+        k = e - s
+        ref = height_ref[s:e].to(dev, non_blocking=True)
+        lab = build_label[s:e].to(dev, non_blocking=True)
+        if pg is not None and k == batch:
+            out = pg(tiles[s:e], k, tiles[e:e + batch] if e + batch <= hi else None)
+        else:
+            x = tiles[s:e].to(dev, non_blocking=True)
+            if k < batch:      # ragged tail: a zero-padded full batch (eval mode: tiles are independent), as predict_tiles runs it
+                x = torch.cat([x, x.new_zeros((batch - k,) + tuple(x.shape[1:]))], 0)
+            out = model(x, features_for_head(net_hr, x[:, :3], model=model))
+        maps = ev.add(out[0][:k], out[1][:k], ref, lab)
+        if keep_maps:
+            ev.maps.append(maps)
+    if hi > lo and hasattr(net_hr, "check_status"):
+        net_hr.check_status()      # one synchronisation per shard: a persistent-trunk timeout raises here instead of scoring NaN features
+    return ev
