@@ -299,6 +299,14 @@ int srbh_rrdbnet_trunk_out(const void* ws, size_t ws_bytes, int num_block, int B
  * extractor BESIDE other work (harness.TrainStep's prefetch stream) leaves CUs free with this.  Returns the previous value. */
 int srbh_ptail_wgs_cap(int cap);
 
+/* Which form of the persistent tail conv kernel the launches of the calling host thread took (same results, different speed -- counted like
+ * srbh_path_counters, so a hot conv sliding back to the general form shows as a count).  counts[0]: the general form (ragged H / W, both
+ * outputs at once); counts[1 + 4 * upsample2x + 2 * lrelu + k]: the full-tile form (H % 8 == 0 && W % 64 == 0) of that conv with only a 16-bit
+ * output (k = 0: ACT16 planes or NHWC16) or only the fp32 NHWC output (k = 1).  Copies min(n, SRBH_PTAIL_FORMS) counters (counts may be NULL),
+ * clears all of them when reset != 0, returns SRBH_PTAIL_FORMS. */
+#define SRBH_PTAIL_FORMS 9
+int srbh_ptail_form_counts(int* counts, int n, int reset);
+
 /* Measurement hook used by bench.py: when on, srbh_rrdbnet_forward() brackets the persistent trunk kernel (the dominant
  * kernel: the 345 dense-block convs, reference SR/rrdbnet_arch.py:136-167) with HIP events on `stream`;
  * srbh_trunk_last_ms() synchronises on the closing event and returns that launch's duration in milliseconds. */

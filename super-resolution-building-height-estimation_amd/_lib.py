@@ -74,6 +74,17 @@ def head_wgs_cap(form):
     return int(cap)
 
 
+PTAIL_FORMS = ("general",) + tuple(f"full_ups{u}_lrelu{l}_{o}" for u in (0, 1) for l in (0, 1) for o in ("out16", "out32"))
+
+
+def ptail_form_counts(reset=False):
+    """{form: launches of the persistent tail conv kernel on this host thread since the last reset} (include/srbh.h srbh_ptail_form_counts)"""
+    buf = (C.c_int * len(PTAIL_FORMS))()
+    n = lib().srbh_ptail_form_counts(buf, len(PTAIL_FORMS), int(reset))
+    assert n == len(PTAIL_FORMS), n
+    return {k: int(v) for k, v in zip(PTAIL_FORMS, buf)}
+
+
 # ---- C structs (mirror include/srbh.h) ------------------------------------------------------------
 class ConvArgs(C.Structure):
     _fields_ = [
@@ -326,6 +337,7 @@ SIGNATURES = {
     "srbh_rrdbnet_last_status": (_i, [_vp, _i, _i, _i, _i, _vp]),
     "srbh_rrdbnet_trunk_out": (_i, [_vp, _sz, _i, _i, _i, _i, _i, _vp, _vp]),
     "srbh_ptail_wgs_cap": (_i, [_i]),
+    "srbh_ptail_form_counts": (_i, [_vp, _i, _i]),
     "srbh_wmse_sum": (_i, [_vp, _vp, _vp, C.c_long, _vp, _vp]),
     "srbh_wmse_grad": (_i, [_vp, _vp, _vp, C.c_long, _vp, _vp, _vp]),
     "srbh_cedice_sums": (_i, [_vp, _i, _i, C.c_long, C.c_long, C.c_long, C.c_long, _vp, _vp, _vp, _vp]),

@@ -46,14 +46,20 @@ __device__ __forceinline__ void tile_origin(const int t, const int tiles_per_img
     X0 = (trem - ty * tiles_x) * TILE_W;
 }
 
-// channel groups 2m and 2m + 1 of block mb of pixel (Y, X) (MFMA D layout: 4 + 4 fp16 values per lane, two dwords each) -> after the half-wave
-// swap every lane holds 8 consecutive channels of its pixel: one 16-byte store into the pixel's record
-__device__ __forceinline__ void store16_pair(const Out16& o, const bool valid, const int img, const int mb, const int Y, const int X, const int m, const int hi,
-                                             const unsigned (&ga)[2], const unsigned (&gb)[2]) {
-    typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
+typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
+
+// channel groups 2m and 2m + 1 of a pixel (MFMA D layout: 4 + 4 fp16 values per lane, two dwords each) -> after the half-wave swap every lane
+// holds 8 consecutive channels of its pixel: the 16 bytes at m * 32 + hi * 16 of the pixel's record
+__device__ __forceinline__ uintx4 pair16(const unsigned (&ga)[2], const unsigned (&gb)[2]) {
     auto s0 = __builtin_amdgcn_permlane32_swap(ga[0], gb[0], false, false);
     auto s1 = __builtin_amdgcn_permlane32_swap(ga[1], gb[1], false, false);
-    const uintx4 raw = {s0[0], s1[0], s0[1], s1[1]};
+    return uintx4{s0[0], s1[0], s0[1], s1[1]};
+}
+
+// channel groups 2m and 2m + 1 of block mb of pixel (Y, X): one 16-byte store into the pixel's record
+__device__ __forceinline__ void store16_pair(const Out16& o, const bool valid, const int img, const int mb, const int Y, const int X, const int m, const int hi,
+                                             const unsigned (&ga)[2], const unsigned (&gb)[2]) {
+    const uintx4 raw = pair16(ga, gb);
     if (valid)
         *(uintx4*)(o.base + (long)img * o.img_b + (long)mb * o.plane_b + (long)(Y + o.border) * o.row_b + (X + o.border) * o.pix_b + m * 32 + hi * 16) = raw;
 }
