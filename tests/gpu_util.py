@@ -1,5 +1,6 @@
 """Thin test-side wrappers that drive individual libsrbh entry points through the C ABI."""
 import ctypes as C
+import math
 
 import torch
 import torch.nn.functional as F
@@ -112,3 +113,46 @@ def run_conv_x16(a, bf16, mask16=None, mask_chunks_total=0, mask_chunk0=0):
 def ref_conv64(x, w, b):
     """float64 conv of the operands AS GIVEN (round them first), float64 result"""
     return F.conv2d(x.double(), w.double(), None if b is None else b.double(), 1, 1)
+
+
+# ---- memory contract of one C-ABI call: writes stay inside the outputs, inputs stay as they were -------------------------------------
+SLACK = 64          # floats of NaN on either side of every output
+
+
+class GuardedBuffers:
+    """the device buffers of one call: inputs with a clone to compare with afterwards, outputs carved out of NaN-filled storage"""
+
+    def __init__(self):
+        self.inputs, self.outputs = [], []
+
+    @staticmethod
+    def _carve(shape, offset):
+        n = math.prod(shape)
+        buf = torch.full((n + 2 * SLACK + 4,), float("nan"), device="cuda:0")
+        view = buf[SLACK + offset: SLACK + offset + n].view(shape)
+        assert buf.data_ptr() % 16 == 0 and view.data_ptr() % 16 == 4 * offset, (buf.data_ptr(), offset)
+        return buf, view
+
+    def inp(self, t, offset=0):
+        """`t` on the device, `offset` floats past a 16-byte boundary"""
+        _, v = self._carve(tuple(t.shape), offset)
+        v.copy_(t)
+        self.inputs.append((v, v.clone()))
+        return v
+
+    def out(self, shape, offset=0, fill=None):
+        buf, v = self._carve(tuple(shape), offset)
+        if fill is not None:
+            v.copy_(fill)
+        self.outputs.append((buf, v))
+        return v
+
+    def verify(self):
+        torch.cuda.synchronize()
+        for v, c in self.inputs:
+            assert torch.equal(v, c), "an input was written"
+        for buf, v in self.outputs:
+            lo = (v.data_ptr() - buf.data_ptr()) // 4
+            assert lo >= SLACK and buf.numel() - lo - v.numel() >= SLACK
+            assert bool(buf[:lo].isnan().all()) and bool(buf[lo + v.numel():].isnan().all()), "a write outside the output"
+            assert not bool(v.isnan().any()), "an output element was left unwritten (or is NaN)"
