@@ -881,6 +881,61 @@ typedef struct srbh_adam_entry {
 int srbh_adam_chunk(void);
 int srbh_adam_step(const srbh_adam_entry* table, const int* chunks, int nchunks, double beta1, double beta2, double eps, void* stream);
 
+/* ---- VGG19 perceptual loss on ACT16 planes (reference SR/srloss.py:61-105 VGGFeatureExtractor, :108-143 PerceptualLoss; wired at
+ * SR/rrdbnet_arch.py:496-498, used at :559-562).  srgan.PerceptualLoss.libsrbh = "f16" runs the feature stack, the loss and its input
+ * gradient on the entry points below.  Arithmetic contract (restated in DESIGN.md 4):
+ *   forward   x_n = (x [+1)/2] - mean) / std in fp32 (each operation rounded as torch's), rounded RNE to fp16: 3 channels of a 32-channel
+ *             plane, the rest zero.  Each conv z = conv(a, w): fp16 operands (srbh_pack_conv3x3_f16's pack), exact products, fp32
+ *             accumulation, fp32 bias.  The plane of a conv that is a cut (a feature) holds rne16(z), the plane of any other conv
+ *             rne16(relu(z)).  The next conv reads relu(plane), behind a pool the 2x2 / stride-2 maximum of it (floor on odd sizes).  ReLU and
+ *             max commute with the rounding: one fp16 rounding per conv defines the whole forward.
+ *   loss      per cut i: w_i * mean |f_i(x) - f_i(gt)| (squared difference for "l2") on the fp16 planes, float64 sums in a fixed order
+ *             (bit-reproducible); the same read writes the loss gradient w_i / N_i * sign(d) (sign(0) = 0; 2 d for l2) as bf16 planes.
+ *   backward  bf16 gradient planes, transposed + flipped weights packed once as bf16 (srbh_pack_conv3x3_b16), fp32 accumulation, each plane
+ *             rounded once to bf16.  At a conv's pre-activation  g_z = [loss gradient of this cut] + (saved plane > 0 ? 1 : 0) *
+ *             pool_backward(g from above);  pool_backward sends the gradient to the FIRST maximum of the window in row-major order (torch's
+ *             tie rule).  dloss/dx leaves as fp32 NCHW, divided by std (and by 2 with the range map), times grad_output.
+ *
+ * srbh_wconv3x3: the wide form of the trunk-family conv (SR/srloss.py:8-48 lists the stack: every conv 3x3 / stride 1 / pad 1, 64..512
+ * channels).  One launch covers all output channels: workgroup = (8 x 64 tile, 64-channel output slice; one 32-channel slice when
+ * cout == 32).  in: 16-bit ACT16 planes, any in_chunks >= 1; w: the ordinary WPACK16 of the whole (cout, 32 * in_chunks) weight
+ * (srbh_pack_conv3x3_f16, or _b16 with bf16 != 0: bf16 input planes, weights and 16-bit outputs); bias: fp32, cout rounded up to 32
+ * floats, or NULL.  Epilogue, in this order: + bias; mask16 != NULL: v = saved fp16 plane > 0 ? v : 0 (ReLU backward); add16 != NULL:
+ * v += planes of the OUTPUT's 16-bit format (the cut's loss gradient); relu: v = max(v, 0).  out16: ACT16 planes, RNE, interior only;
+ * out32: fp32 NHWC with out32_c <= cout channels per pixel (the unrounded values).  cout: 32 or a multiple of 64. */
+typedef struct srbh_wconv3x3_args {
+    const void* in; int in_chunks_total, in_chunk0, in_chunks;
+    const void* w; const float* bias; int cout;
+    int B, H, W;
+    int bf16, relu;
+    const void* mask16; int mask_chunks_total, mask_chunk0;
+    const void* add16; int add_chunks_total, add_chunk0;
+    void* out16; int out16_chunks_total, out16_chunk0;
+    float* out32; int out32_c;
+} srbh_wconv3x3_args;
+int srbh_wconv3x3(const srbh_wconv3x3_args* a, void* stream);
+/* SR/srloss.py:97-100 (range map, input normalisation): x fp32 NCHW (B, 3, H, W) -> one fp16 ACT16 plane (channels 3..31 zero), interior only.
+ * mean / std: 3 host floats each, or both NULL (no normalisation); range_norm != 0: (x + 1) / 2 first. */
+int srbh_vgg_input_f16(const float* x, void* plane, int B, int H, int W, const float* mean, const float* std_, int range_norm, void* stream);
+/* SR/srloss.py:101-105 runs nn.ReLU / nn.MaxPool2d(2, 2) between the convs: out = relu(in), or (pool != 0) the 2x2 / stride-2 maximum of
+ * relu(in) on (H / 2) x (W / 2) planes (floor).  fp16 ACT16 planes, `chunks` of them per image in both buffers, interior only. */
+int srbh_vgg_relu_pool_f16(const void* in, void* out, int B, int chunks, int H, int W, int pool, void* stream);
+/* the backward of the above at a conv's pre-activation (autograd of SR/srloss.py:135-141's loss through :101-105):
+ *   out = [add] + (saved > 0 ? 1 : 0) * route(g),   route = identity (pool == 0, g on H x W planes) or the max-pool backward (pool != 0, g on
+ * (H / 2) x (W / 2) planes): the gradient of a window goes to its first maximum of relu(saved) in row-major order; pixels outside every window
+ * (odd sizes) get none.  g, add (may be NULL), out: bf16 planes; saved: the fp16 plane the forward stored; fp32 sum, one RNE rounding. */
+int srbh_vgg_relu_pool_bwd_b16(const void* g, const void* saved, const void* add, void* out, int B, int chunks, int H, int W, int pool, void* stream);
+/* SR/srloss.py:135-141, one cut: d = fx - fg on fp16 planes (B, 32 * chunks, H, W).  acc[0] = (accumulate ? acc[0] : 0) + coef * S with
+ * S = sum |d| (l2: sum d^2) in float64, fixed order (per-workgroup slots of ws, then an ordered fold; no atomics).  grad != NULL: bf16
+ * planes of gscale * sign(d) (l2: gscale * d, d = fx - fg in fp32; pass gscale = 2 w / N), gscale rounded to fp32 by the caller.
+ * ws: srbh_vgg_dist_ws_bytes bytes of device memory, no initialisation needed. */
+size_t srbh_vgg_dist_ws_bytes(int B, int chunks, int H, int W);
+int srbh_vgg_dist(const void* fx, const void* fg, int B, int chunks, int H, int W, int l2, double coef, int accumulate, double* acc, float gscale,
+                  void* grad, void* ws, void* stream);
+/* the last step of the input gradient: g fp32 NHWC (B, H, W, 3) (srbh_wconv3x3's out32 of the first conv's data gradient) -> dx fp32 NCHW,
+ * dx = g / std[c] (/ 2 with range_norm) * *grad_output (a DEVICE scalar).  std_: 3 host floats or NULL. */
+int srbh_vgg_dx_nchw(const float* g, float* dx, int B, int H, int W, const float* std_, int range_norm, const float* grad_output, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,7 +17,7 @@ CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(ROOT, "include")
 LIB_PATH = os.path.join(_HERE, "libsrbh.so")
 _DEV_LIB = os.environ.get("SRBH_LIB_PATH")      # developer A/B only (tools/ab_variants.sh): load another build of the same ABI
-SOURCES = ["srbh_conv3x3.hip", "srbh_aux.hip", "srbh_rrdbnet.hip", "srbh_ptrunk.hip", "srbh_trunk_wgrad.hip", "srbh_ptail.hip", "srbh_ptail_split.hip", "srbh_head.hip", "srbh_head_bwd.hip", "srbh_mosaic.hip", "srbh_loader.hip", "srbh_loss.hip", "srbh_sr_metrics.hip", "srbh_eval.hip", "srbh_dwconv.hip", "srbh_mbconv.hip", "srbh_pwconv.hip", "srbh_dconv.hip", "srbh_optim.hip"]
+SOURCES = ["srbh_conv3x3.hip", "srbh_aux.hip", "srbh_rrdbnet.hip", "srbh_ptrunk.hip", "srbh_trunk_wgrad.hip", "srbh_ptail.hip", "srbh_ptail_split.hip", "srbh_head.hip", "srbh_head_bwd.hip", "srbh_mosaic.hip", "srbh_loader.hip", "srbh_loss.hip", "srbh_sr_metrics.hip", "srbh_eval.hip", "srbh_dwconv.hip", "srbh_mbconv.hip", "srbh_pwconv.hip", "srbh_dconv.hip", "srbh_optim.hip", "srbh_vgg.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # NOTE: `-mllvm -amdgpu-mfma-vgpr-form=1` (accumulators in VGPRs: no v_accvgpr copies at K-loop back-edges).  Round 1 saw the
 # first persistent trunk kernel produce non-deterministic garbage with it; round 3 re-ran it on the current kernel (ptrunk3:
@@ -199,6 +199,19 @@ class ConvSplit(C.Structure):
     ]
 
 
+class WConvArgs(C.Structure):
+    _fields_ = [
+        ("in_", C.c_void_p), ("in_chunks_total", C.c_int), ("in_chunk0", C.c_int), ("in_chunks", C.c_int),
+        ("w", C.c_void_p), ("bias", C.c_void_p), ("cout", C.c_int),
+        ("B", C.c_int), ("H", C.c_int), ("W", C.c_int),
+        ("bf16", C.c_int), ("relu", C.c_int),
+        ("mask16", C.c_void_p), ("mask_chunks_total", C.c_int), ("mask_chunk0", C.c_int),
+        ("add16", C.c_void_p), ("add_chunks_total", C.c_int), ("add_chunk0", C.c_int),
+        ("out16", C.c_void_p), ("out16_chunks_total", C.c_int), ("out16_chunk0", C.c_int),
+        ("out32", C.c_void_p), ("out32_c", C.c_int),
+    ]
+
+
 class EvalArgs(C.Structure):
     _fields_ = [("height", C.c_void_p), ("height_bs", C.c_long),
                 ("logits", C.c_void_p), ("logits_bs", C.c_long), ("logits_cs", C.c_long), ("logits_ps", C.c_long),
@@ -350,6 +363,13 @@ SIGNATURES = {
     "srbh_sr_cpsnr_sums": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "srbh_eval_ws_bytes": (_sz, [_i, _i, _i]),
     "srbh_eval_sums": (_i, [C.POINTER(EvalArgs), _vp]),
+    "srbh_wconv3x3": (_i, [C.POINTER(WConvArgs), _vp]),
+    "srbh_vgg_input_f16": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),
+    "srbh_vgg_relu_pool_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "srbh_vgg_relu_pool_bwd_b16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "srbh_vgg_dist_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "srbh_vgg_dist": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.c_double, _i, _vp, _f, _vp, _vp, _vp]),
+    "srbh_vgg_dx_nchw": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     "srbh_trunk_timing": (_i, [_i]),
     "srbh_trunk_last_ms": (_i, [C.POINTER(C.c_float)]),
     "srbh_trunk_kernel_name": (C.c_char_p, []),

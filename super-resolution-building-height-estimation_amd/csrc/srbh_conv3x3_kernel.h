@@ -65,6 +65,21 @@ struct KParams {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
+// the WIDE form (srbh_wconv3x3, 64..512 channels): a workgroup owns a 64- (or 32-) channel SLICE of the output; the kernel shifts w / bias / out16 /
+// mask16 / add16 / out32_c0 to its slice before it calls conv_tile.  The pack is the ordinary WPACK16 of the whole (cout, cin) weight, whose
+// chunk holds 18 x w_nmb fragments: the slice's CB fragments of each (tap, k-step) lie w_nmb KiB apart.
+struct WKParams : KParams {
+    int w_nmb;              // cout / 32 of the pack
+    int w_chunk_b;          // bytes of one input chunk of the pack: 18 KiB x w_nmb
+    int nslice;
+    int relu;               // max(v, 0) on the stored values
+    int out32_c0;           // first channel of this slice in the fp32 NHWC output (out32_c channels per pixel)
+    const char* add16;      // ACT16 planes of the output's format (bf16 with BF == 1, else fp16) added behind the mask
+    long add_img_b;
+    int add_plane_b;
+    int add_row_b;
+};
+
 // dynamic LDS of one workgroup: two pipeline stages, or the epilogue transpose slices, whichever is larger
 template <int CB, int UPS>
 constexpr int lds_bytes() {
@@ -88,7 +103,9 @@ __device__ __forceinline__ int xcd_remap(int bid, int n) {
 // BF = 1: bf16 operands (gradients: fp32's exponent range, no loss scaling) -- the staged 16-bit records and the packed weights are
 // bf16, the products run on v_mfma_f32_32x32x16_bf16 and a 16-bit output is rounded to bf16 (RNE); everything else is identical.
 // BF = 2: bf16 operands as BF = 1, the 16-bit output rounded to fp16 (the bf16 inference trunk's last conv5: its planes leave for conv_body).
-template <int CB, int UPS, int ABL, int PERSIST, int BF = 0>
+// WIDE = 1: p is a WKParams; weight fragments are fetched at the wide pack's stride, the epilogue is ReLU (slope 0) instead of LeakyReLU --
+// mask (saved plane > 0 ? v : 0), then the addend planes, then ReLU -- and the fp32 output takes the slice's channel offset.
+template <int CB, int UPS, int ABL, int PERSIST, int BF = 0, int WIDE = 0>
 __device__ __forceinline__ void conv_tile(const KParams& p, char* smem, const int img, const int Y0, const int X0,
                                           unsigned long long* tstamp) {
     using G = TileGeo<UPS>;
@@ -132,8 +149,19 @@ __device__ __forceinline__ void conv_tile(const KParams& p, char* smem, const in
                 __builtin_amdgcn_global_load_lds(GPTR(s + goff[j < G::NJ ? j : 0]),
                                                  LPTR(dst + (j * 256 + wave * 64) * 16), 16, 0, PERSIST ? 16 : 0);
         }
-        const char* ws = wsrc + (long)chunk * W_B;
         char* wdst = dst + G::IN_B;
+        if constexpr (WIDE) {     // the slice's CB fragments of each (tap, k-step) out of the whole weight's pack
+            const WKParams& wp = static_cast<const WKParams&>(p);
+            const char* ws = wsrc + (long)chunk * wp.w_chunk_b;
+#pragma unroll
+            for (int kk = 0; kk < WPP; ++kk) {
+                const int f = wave + 4 * (part * WPP + kk);
+                if (part * WPP + kk < WFR && f < 18 * CB)
+                    __builtin_amdgcn_global_load_lds(GPTR(ws + ((f / CB) * wp.w_nmb + f % CB) * 1024), LPTR(wdst + f * 1024), 16, 0, 0);
+            }
+            return;
+        }
+        const char* ws = wsrc + (long)chunk * W_B;
 #pragma unroll
         for (int kk = 0; kk < WPP; ++kk) {
             const int f = wave + 4 * (part * WPP + kk);
@@ -346,14 +374,54 @@ __device__ __forceinline__ void conv_tile(const KParams& p, char* smem, const in
                         v0 += *(const floatx4*)sk;
                         v1 += *(const floatx4*)(sk + 4);
                     }
-                    if (p.lrelu) {
+                    if constexpr (WIDE) {
+                        const WKParams& wp = static_cast<const WKParams&>(p);
+                        if (p.mask16) {   // ReLU backward with the SAVED plane (> 0 ? 1 : 0, torch's threshold_backward)
+                            const half8 mv = *(const half8*)(p.mask16 + (long)img * p.mask_img_b + (long)(c8 >> 2) * p.mask_plane_b +
+                                                             (long)(Y + 1) * p.mask_row_b + (X + 1) * PIX_B + (c8 & 3) * 16);
+#pragma unroll
+                            for (int q = 0; q < 4; ++q) {
+                                v0[q] = (float)mv[q] > 0.f ? v0[q] : 0.f;
+                                v1[q] = (float)mv[4 + q] > 0.f ? v1[q] : 0.f;
+                            }
+                        }
+                        if (wp.add16) {
+                            const half8 av = *(const half8*)(wp.add16 + (long)img * wp.add_img_b + (long)(c8 >> 2) * wp.add_plane_b +
+                                                             (long)(Y + 1) * wp.add_row_b + (X + 1) * PIX_B + (c8 & 3) * 16);
+                            if constexpr (BF == 1) {
+                                typedef unsigned uint4e __attribute__((ext_vector_type(4)));
+                                const uint4e au = __builtin_bit_cast(uint4e, av);
+#pragma unroll
+                                for (int q = 0; q < 2; ++q) {
+                                    v0[2 * q] += __builtin_bit_cast(float, au[q] << 16);
+                                    v0[2 * q + 1] += __builtin_bit_cast(float, au[q] & 0xffff0000u);
+                                    v1[2 * q] += __builtin_bit_cast(float, au[2 + q] << 16);
+                                    v1[2 * q + 1] += __builtin_bit_cast(float, au[2 + q] & 0xffff0000u);
+                                }
+                            } else {
+#pragma unroll
+                                for (int q = 0; q < 4; ++q) {
+                                    v0[q] += (float)av[q];
+                                    v1[q] += (float)av[4 + q];
+                                }
+                            }
+                        }
+                        if (wp.relu) {
+#pragma unroll
+                            for (int q = 0; q < 4; ++q) {
+                                v0[q] = v0[q] > 0.f ? v0[q] : 0.f;
+                                v1[q] = v1[q] > 0.f ? v1[q] : 0.f;
+                            }
+                        }
+                    }
+                    if (!WIDE && p.lrelu) {
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
                             v0[q] = v0[q] >= 0.f ? v0[q] : v0[q] * 0.2f;
                             v1[q] = v1[q] >= 0.f ? v1[q] : v1[q] * 0.2f;
                         }
                     }
-                    if (p.mask16) {   // LeakyReLU backward with the SAVED post-activation (y > 0 <=> z > 0; slope 0.2 at z <= 0 as torch)
+                    if (!WIDE && p.mask16) {   // LeakyReLU backward with the SAVED post-activation (y > 0 <=> z > 0; slope 0.2 at z <= 0 as torch)
                         const half8 mv = *(const half8*)(p.mask16 + (long)img * p.mask_img_b + (long)(c8 >> 2) * p.mask_plane_b +
                                                          (long)(Y + 1) * p.mask_row_b + (X + 1) * PIX_B + (c8 & 3) * 16);
 #pragma unroll
@@ -391,7 +459,22 @@ __device__ __forceinline__ void conv_tile(const KParams& p, char* smem, const in
                             *(half8*)o = hv;
                         }
                     }
-                    if (p.out32) {
+                    if constexpr (WIDE) {
+                        if (p.out32) {
+                            const int c0 = static_cast<const WKParams&>(p).out32_c0 + c8 * 8;
+                            float* o = p.out32 + pix * p.out32_c + c0;
+                            if ((p.out32_c & 7) == 0 && c0 + 8 <= p.out32_c) {
+                                *(floatx4*)o = v0;
+                                *(floatx4*)(o + 4) = v1;
+                            } else {
+#pragma unroll
+                                for (int q = 0; q < 4; ++q) {
+                                    if (c0 + q < p.out32_c) o[q] = v0[q];
+                                    if (c0 + 4 + q < p.out32_c) o[4 + q] = v1[q];
+                                }
+                            }
+                        }
+                    } else if (p.out32) {
                         float* o = p.out32 + pix * p.out32_c + c8 * 8;
                         if (p.out32_c == 64) {
                             *(floatx4*)o = v0;
@@ -425,6 +508,26 @@ __global__ __launch_bounds__(256, 1) void conv3x3_f16_kernel(const KParams p) {
         if (threadIdx.x == 0)
             for (int k = 0; k < 8; ++k) p.prof[blockIdx.x * 8 + k] = tstamp[k];
     }
+}
+
+// The wide form's kernel: grid = tiles x nslice, consecutive ids of one XCD walk the slices of ONE tile (they share the staged input in L2).
+template <int CB, int BF>
+__global__ __launch_bounds__(256, 1) void wconv3x3_kernel(const WKParams p0) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    unsigned long long tstamp[8];
+    const int l = xcd_remap(blockIdx.x, p0.nblocks);
+    const int t = l / p0.nslice, s = l - t * p0.nslice;
+    WKParams p = p0;
+    p.w = p0.w + (long)s * CB * 1024;
+    if (p0.bias) p.bias = p0.bias + s * CB * 32;
+    if (p0.out16) p.out16 = p0.out16 + (long)s * CB * p0.out16_plane_b;
+    if (p0.mask16) p.mask16 = p0.mask16 + (long)s * CB * p0.mask_plane_b;
+    if (p0.add16) p.add16 = p0.add16 + (long)s * CB * p0.add_plane_b;
+    p.out32_c0 = s * CB * 32;
+    const int img = t / p.tiles_per_img;
+    const int trem = t - img * p.tiles_per_img;
+    const int ty = trem / p.tiles_x, tx = trem - ty * p.tiles_x;
+    conv_tile<CB, 0, 0, 0, BF, 1>(p, smem, img, ty * TILE_H, tx * TILE_W, tstamp);
 }
 
 }  // namespace srbh_k

@@ -658,6 +658,11 @@ class RealESRGAN:
         sel = os.environ.get("SRBH_SR_DISC", "")
         use = on_gpu and (sel == "libsrbh" or (sel != "stock" and RA._mixed()))
         self.net_d.libsrbh = ("f16" if RA._mixed() else "f32") if use else None
+        # The VGG19 stack behind the perceptual term on libsrbh's 16-bit kernels (srgan._PerceptualFn): opt-in, SRBH_SR_VGG=libsrbh, for an
+        # srgan.PerceptualLoss on the device only (a foreign plug-in module keeps its own forward).
+        from .srgan import PerceptualLoss as _PL
+        if on_gpu and os.environ.get("SRBH_SR_VGG", "") == "libsrbh" and isinstance(self.cri_perceptual, _PL):
+            self.cri_perceptual.libsrbh = "f16"
 
         def update(optimizer, train_d, groups):
             self.net_d.requires_grad_(train_d)

@@ -321,9 +321,223 @@ class VGGFeatureExtractor(nn.Module):
         return self.features(x)
 
 
+# ---- the same loss on libsrbh (PerceptualLoss.libsrbh = "f16") ---------------------------------------------------------------------------
+# One call runs the feature stack on the output and on the target, the loss and (when x requires grad) dloss/dx on hand-written kernels:
+# csrc/srbh_conv3x3.hip srbh_wconv3x3 (the trunk-family conv for 64..512 channels) and csrc/srbh_vgg.hip (input conversion, ReLU / max-pool
+# plane -> plane and its backward, the one-read feature distance).  Activations are fp16 ACT16 planes from the input conversion to the last
+# feature, gradients bf16 planes; the arithmetic contract stands in include/srbh.h and DESIGN.md 4.  No stock convolution, no fallback.
+def _vgg_plan(pl):
+    """[(conv module, is_cut, pool_behind)] of the convs up to the last cut + the cut weights; NotImplementedError for a cut that is no conv"""
+    feats = pl.vgg.features
+    if pl.vgg.list_outputs:
+        layers, cuts = [], []
+        for child in feats.children():
+            layers += list(child.children())
+            cuts.append(len(layers) - 1)
+        weights = [float(w) for w in pl.weights[:len(cuts)]]
+    else:
+        layers = list(feats.children())
+        cuts, weights = [len(layers) - 1], [1.0]
+    for c in cuts:
+        if c < 0 or not isinstance(layers[c], nn.Conv2d):
+            raise NotImplementedError(f"PerceptualLoss.libsrbh: cut {c} is not a convolution of vgg19_features() "
+                                      f"({type(layers[c]).__name__ if c >= 0 else 'empty'}); the libsrbh mode takes cuts at conv indices only")
+    if sorted(set(cuts)) != cuts:
+        raise NotImplementedError(f"PerceptualLoss.libsrbh: cuts {cuts} are not strictly increasing")
+    plan, i = [], 0
+    while i <= cuts[-1]:
+        conv = layers[i]
+        if not (isinstance(conv, nn.Conv2d) and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)):
+            raise NotImplementedError(f"PerceptualLoss.libsrbh: layer {i} is not a 3x3 / stride 1 / pad 1 convolution")
+        j, relu, pool = i + 1, False, False
+        while j <= cuts[-1] and not isinstance(layers[j], nn.Conv2d):
+            if isinstance(layers[j], nn.ReLU) and not pool:
+                relu = True
+            elif isinstance(layers[j], nn.MaxPool2d) and relu and not pool:
+                pool = True
+            else:
+                raise NotImplementedError(f"PerceptualLoss.libsrbh: layer {j} does not follow the conv / ReLU / max-pool order of vgg19_features()")
+            j += 1
+        if j <= cuts[-1] and not relu:
+            raise NotImplementedError(f"PerceptualLoss.libsrbh: no ReLU behind conv {i}")
+        plan.append((conv, i in cuts, pool, i))
+        i = j
+    return plan, cuts, weights
+
+
+def _vgg_packs(pl, device):
+    """frozen packs of the plan's convs: fp16 forward packs + fp32 biases, bf16 transposed + flipped packs; keyed by the wcache stamps"""
+    from . import _lib, wcache
+    plan, cuts, weights = _vgg_plan(pl)
+    params = [p for conv, *_ in plan for p in (conv.weight, conv.bias)]
+    key = (wcache.gen(*params), tuple((p._version, p.data_ptr()) for p in params), tuple(cuts), str(device))
+    cached = pl.__dict__.get("_srbh_vgg_packs")
+    if cached is None or cached[0] != key:
+        L = _lib.lib()
+        convs = []
+        for conv, is_cut, pool, idx in plan:
+            w = conv.weight.detach().float().contiguous()
+            cout, cin = w.shape[:2]
+            if cout % 64 or (cin % 32 and cin != 3) or conv.bias is None:
+                raise NotImplementedError(f"PerceptualLoss.libsrbh: conv {idx} has {cin} -> {cout} channels")
+            fwd = torch.zeros(L.srbh_wpack16_bytes(cout, cin), dtype=torch.uint8, device=device)
+            _lib.check(L.srbh_pack_conv3x3_f16(w.data_ptr(), cout, cin, fwd.data_ptr(), _lib.stream_ptr()), "pack_conv3x3_f16(vgg)")
+            wt = w.transpose(0, 1).flip(2, 3).contiguous()
+            bwd = torch.zeros(L.srbh_wpack16_bytes(cin, cout), dtype=torch.uint8, device=device)
+            _lib.check(L.srbh_pack_conv3x3_b16(wt.data_ptr(), cin, cout, bwd.data_ptr(), _lib.stream_ptr()), "pack_conv3x3_b16(vgg)")
+            convs.append(dict(fwd=fwd, bwd=bwd, bias=conv.bias.detach().float().contiguous(), cin=cin, cout=cout, cut=is_cut, pool=pool))
+        import ctypes as C
+        norm = None
+        if pl.vgg.use_input_norm:
+            norm = ((C.c_float * 3)(*pl.vgg.mean.flatten().tolist()), (C.c_float * 3)(*pl.vgg.std.flatten().tolist()))
+        cached = (key, dict(convs=convs, weights=weights, norm=norm))
+        pl.__dict__["_srbh_vgg_packs"] = cached
+    wcache.keep(cached)
+    return cached[1]
+
+
+class _PlanePool:
+    """zero-bordered ACT16 buffers of one (device, batch) per (tag, chunks, H, W): allocated and zeroed once, the kernels write interiors only"""
+
+    def __init__(self, device, B):
+        self.device, self.B, self.bufs = device, B, {}
+
+    def get(self, tag, chunks, H, W):
+        from . import _lib, wcache
+        k = (tag, chunks, H, W)
+        b = self.bufs.get(k)
+        if b is None:
+            b = self.bufs[k] = torch.zeros(_lib.lib().srbh_act16_bytes(self.B, chunks * 32, H, W), dtype=torch.uint8, device=self.device)
+        wcache.keep(b)
+        return b
+
+
+def _wconv(inp, in_chunks, w, bias, cout, B, H, W, bf16=0, relu=0, mask=None, add=None, out16=None, out32=None, out32_c=0):
+    import ctypes as C
+    from . import _lib
+    a = _lib.WConvArgs()
+    a.in_, a.in_chunks_total, a.in_chunk0, a.in_chunks = inp.data_ptr(), in_chunks, 0, in_chunks
+    a.w, a.bias, a.cout = w.data_ptr(), (None if bias is None else bias.data_ptr()), cout
+    a.B, a.H, a.W, a.bf16, a.relu = B, H, W, bf16, relu
+    if mask is not None:
+        a.mask16, a.mask_chunks_total, a.mask_chunk0 = mask.data_ptr(), cout // 32, 0
+    if add is not None:
+        a.add16, a.add_chunks_total, a.add_chunk0 = add.data_ptr(), cout // 32, 0
+    if out16 is not None:
+        a.out16, a.out16_chunks_total, a.out16_chunk0 = out16.data_ptr(), cout // 32, 0
+    if out32 is not None:
+        a.out32, a.out32_c = out32.data_ptr(), out32_c
+    _lib.check(_lib.lib().srbh_wconv3x3(C.byref(a), _lib.stream_ptr()), "wconv3x3(vgg)")
+
+
+class _PerceptualFn(torch.autograd.Function):
+    """the whole loss: forward returns the fp32 loss and keeps the fp32 NHWC gradient of the normalised input; backward scales it"""
+
+    @staticmethod
+    def forward(ctx, x, gt, pl):
+        from . import _lib
+        L, sp = _lib.lib(), _lib.stream_ptr
+        dev = x.device
+        P = _vgg_packs(pl, dev)
+        convs, norm = P["convs"], P["norm"]
+        B, C3, H0, W0 = x.shape
+        if C3 != 3 or tuple(gt.shape) != tuple(x.shape):
+            raise ValueError(f"PerceptualLoss.libsrbh: x and gt must be (B, 3, H, W) of one shape (got {tuple(x.shape)}, {tuple(gt.shape)})")
+        pools = pl.__dict__.setdefault("_srbh_vgg_planes", {})
+        pool = pools.get((str(dev), B))
+        if pool is None:
+            pool = pools[(str(dev), B)] = _PlanePool(dev, B)
+        rng = int(bool(pl.vgg.use_range_norm))
+        mean_p, std_p = (norm if norm is not None else (None, None))
+        l2 = int(pl.lossfn_type != "l1")
+        want_grad = bool(ctx.needs_input_grad[0])
+
+        def features(t, side):
+            """planes of every conv ('x': all kept for the backward; 'g': only the cuts are kept, the rest ping-pong)"""
+            src = t.detach().float().contiguous()
+            a = pool.get("in", 1, H0, W0)
+            _lib.check(L.srbh_vgg_input_f16(src.data_ptr(), a.data_ptr(), B, H0, W0, mean_p, std_p, rng, sp()), "vgg_input_f16")
+            h, w, ach, out = H0, W0, 1, []
+            for j, c in enumerate(convs):
+                nch = c["cout"] // 32
+                tag = f"{side}{j}" if (side == "x" or c["cut"]) else f"g_pp{j & 1}"
+                p = pool.get(tag, nch, h, w)
+                _wconv(a, ach, c["fwd"], c["bias"], c["cout"], B, h, w, relu=int(not c["cut"]), out16=p)
+                out.append((p, nch, h, w))
+                if j + 1 < len(convs):
+                    if c["cut"] or c["pool"]:
+                        if c["pool"] and (h < 2 or w < 2):
+                            raise ValueError(f"PerceptualLoss.libsrbh: a {h}x{w} plane cannot be pooled")
+                        ho, wo = (h // 2, w // 2) if c["pool"] else (h, w)
+                        a = pool.get(f"a{j & 1}", nch, ho, wo)
+                        _lib.check(L.srbh_vgg_relu_pool_f16(p.data_ptr(), a.data_ptr(), B, nch, h, w, int(c["pool"]), sp()), "vgg_relu_pool_f16")
+                        h, w = ho, wo
+                    else:
+                        a = p
+                    ach = nch
+            return out
+
+        with torch.cuda.device(dev):
+            fx, fg = features(x, "x"), features(gt, "g")
+            acc = torch.empty(1, dtype=torch.float64, device=dev)
+            lg, first, wi = {}, True, 0
+            for j, c in enumerate(convs):
+                if not c["cut"]:
+                    continue
+                (px, nch, h, w), (pg, *_) = fx[j], fg[j]
+                n = B * c["cout"] * h * w
+                wgt = P["weights"][wi]
+                wi += 1
+                g = pool.get(f"lg{j}", nch, h, w) if want_grad else None
+                ws = torch.empty(max(1, L.srbh_vgg_dist_ws_bytes(B, nch, h, w) // 8), dtype=torch.float64, device=dev)
+                gscale = (2.0 if l2 else 1.0) * wgt / n
+                _lib.check(L.srbh_vgg_dist(px.data_ptr(), pg.data_ptr(), B, nch, h, w, l2, wgt / n, int(not first), acc.data_ptr(), gscale,
+                                           None if g is None else g.data_ptr(), ws.data_ptr(), sp()), "vgg_dist")
+                lg[j] = g
+                first = False
+            ctx.geo = None
+            if want_grad:
+                j = len(convs) - 1
+                G = lg[j]
+                while j > 0:
+                    c, prev = convs[j], convs[j - 1]
+                    _, _, h, w = fx[j]
+                    pp, pch, ph, pw = fx[j - 1]
+                    add = lg.get(j - 1)
+                    Gp = pool.get(f"G_pp{j & 1}", pch, ph, pw)
+                    if prev["pool"]:
+                        T = pool.get("T", pch, h, w)
+                        _wconv(G, c["cout"] // 32, c["bwd"], None, c["cin"], B, h, w, bf16=1, out16=T)
+                        _lib.check(L.srbh_vgg_relu_pool_bwd_b16(T.data_ptr(), pp.data_ptr(), None if add is None else add.data_ptr(), Gp.data_ptr(),
+                                                                B, pch, ph, pw, 1, sp()), "vgg_relu_pool_bwd_b16")
+                    else:
+                        _wconv(G, c["cout"] // 32, c["bwd"], None, c["cin"], B, h, w, bf16=1, mask=pp, add=add, out16=Gp)
+                    G = Gp
+                    j -= 1
+                g3 = torch.empty((B, H0, W0, 3), dtype=torch.float32, device=dev)
+                _wconv(G, convs[0]["cout"] // 32, convs[0]["bwd"], None, 32, B, H0, W0, bf16=1, out32=g3, out32_c=3)
+                ctx.save_for_backward(g3)
+                ctx.geo = (B, H0, W0, rng, None if norm is None else norm[1])
+            return (acc.to(torch.float32) * float(pl.loss_weight)).reshape(())
+
+    @staticmethod
+    def backward(ctx, go):
+        from . import _lib
+        (g3,) = ctx.saved_tensors
+        B, H0, W0, rng, std_p = ctx.geo
+        dx = torch.empty((B, 3, H0, W0), dtype=torch.float32, device=g3.device)
+        gof = go.detach().float().reshape(1).contiguous()
+        with torch.cuda.device(g3.device):
+            _lib.check(_lib.lib().srbh_vgg_dx_nchw(g3.data_ptr(), dx.data_ptr(), B, H0, W0, std_p, rng, gof.data_ptr(), _lib.stream_ptr()), "vgg_dx_nchw")
+        return dx, None, None
+
+
 class PerceptualLoss(nn.Module):
     """SR/srloss.py:108-143: sum_i weights[i] * L1|MSE(vgg_i(x), vgg_i(gt.detach())) -- times `self.loss_weight`, which upstream pins to 1.0
-    whatever the argument says (srloss.py:123: kept, it is the arithmetic the checkpoints were trained with)."""
+    whatever the argument says (srloss.py:123: kept, it is the arithmetic the checkpoints were trained with).
+    `libsrbh = "f16"` (device tensors only): the feature stack, the loss and its input gradient on libsrbh's 16-bit kernels (_PerceptualFn)."""
+
+    libsrbh = None          # None: stock ops; "f16": fp16 activation planes / bf16 gradient planes on libsrbh, cuts at conv indices only
 
     def __init__(self, feature_layer=(2, 7, 16, 25, 34), weights=(0.1, 0.1, 1.0, 1.0, 1.0), lossfn_type="l1", use_input_norm=True,
                  use_range_norm=False, loss_weight=1.0, state_dict=None):
@@ -336,6 +550,10 @@ class PerceptualLoss(nn.Module):
         self.loss_weight = 1.0
 
     def forward(self, x, gt):
+        if self.libsrbh is not None and x.is_cuda:
+            if self.libsrbh != "f16":
+                raise ValueError(f"PerceptualLoss.libsrbh: unknown mode {self.libsrbh!r} (None or 'f16')")
+            return _PerceptualFn.apply(x, gt.detach(), self)
         x_vgg, gt_vgg = self.vgg(x), self.vgg(gt.detach())
         loss = 0.0
         if isinstance(x_vgg, list):
