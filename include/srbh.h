@@ -426,7 +426,8 @@ int srbh_bn_finalize_clear(double* stats, int C, double count, const float* gamm
 int srbh_bn_eval_scale_shift(int C, const float* gamma, const float* beta, const float* running_mean,
                              const float* running_var, float eps, float* scale, float* shift, void* stream);
 /* out = relu(a*a_scale + a_shift + (idt*i_scale + i_shift))   (BasicBlock tail, SR/HRfuse.py:150-157);
- * i_scale NULL = identity path without downsample */
+ * i_scale NULL = identity path without downsample.  C % 4 == 0; a, idt, out and the per-channel vectors are read as 4-channel groups:
+ * 16-byte aligned (8 bytes for a tensor that holds fp16), anything else is refused. */
 int srbh_bn_add_relu(const float* a, const float* a_scale, const float* a_shift, const float* idt,
                      const float* i_scale, const float* i_shift, float* out, long npix, int C, void* stream);
 /* The same pass with fp16 tensors in memory (round 3: the training step keeps the block-internal activations c1 / c2 / downsample
@@ -558,7 +559,9 @@ int srbh_bn_bwd_apply(const float* g, const float* c, const float* mean, const f
  * gradient tensors that live INSIDE one BasicBlock's backward are bf16 (SRBH_BN_G_B16: g; SRBH_BN_OUT_B16: dz_out / out -- their
  * consumers round their operands to bf16 anyway), the saved activation c is fp16 (SRBH_BN_C_H16); relu_ref stays fp32; the
  * arithmetic is fp32, and with a bf16 dz_out the sums are taken over the rounded values (what the consumers read).
- * srbh_bn_bwd_reduce_io: relu_ref / dz_out as srbh_bn_bwd_reduce_relu (may be NULL), mask_* as srbh_bn_bwd_reduce. */
+ * srbh_bn_bwd_reduce_io: relu_ref / dz_out as srbh_bn_bwd_reduce_relu (may be NULL), mask_* as srbh_bn_bwd_reduce.
+ * Without a dz_out nothing is rounded: the sums are those of the masked g.  srbh_bn_bwd_apply_io refuses tensors and per-channel
+ * vectors that are not 16-byte aligned (8 bytes for a 16-bit tensor).  A refused call of any of these writes nothing, `stats` included. */
 #define SRBH_BN_OUT_B16 1
 #define SRBH_BN_C_H16 2
 #define SRBH_BN_G_B16 4

@@ -1025,6 +1025,11 @@ static int bn_add_relu_impl(const void* a, const float* a_scale, const float* a_
                             const float* i_shift, float* out, long npix, int C, int io, void* stream, unsigned long long* bits = nullptr) {
     SRBH_REQUIRE(a && a_scale && a_shift && idt && out && npix > 0 && C > 0 && C % 4 == 0, "srbh_bn_add_relu: bad arguments");
     SRBH_REQUIRE((io & ~3) == 0, "srbh_bn_add_relu_io: unknown io bits");
+    SRBH_REQUIRE(!i_scale || i_shift, "srbh_bn_add_relu: i_scale needs i_shift");
+    // a 4-channel group is one 16-byte access (8 bytes where the tensor holds fp16), the per-channel vectors are read as 16-byte groups
+    SRBH_REQUIRE(((uintptr_t)a & ((io & 1) ? 7 : 15)) == 0 && ((uintptr_t)idt & ((io & 2) ? 7 : 15)) == 0 && ((uintptr_t)out & 15) == 0 &&
+                 (((uintptr_t)a_scale | (uintptr_t)a_shift | (uintptr_t)i_scale | (uintptr_t)i_shift) & 15) == 0,
+                 "srbh_bn_add_relu: unaligned tensor or per-channel vector (16 bytes; 8 for an fp16 tensor)");
     long n4 = npix * C / 4;
     int blocks = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
 #define SRBH_BAR(A_, I_) hipLaunchKernelGGL((bn_add_relu_kernel<A_, I_>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, a_scale, a_shift, \

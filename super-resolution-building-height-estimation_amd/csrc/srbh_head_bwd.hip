@@ -902,7 +902,7 @@ extern "C" int srbh_add_inplace(float* a, const float* b, long n, void* stream) 
 static int bn_bwd_reduce_impl(const void* g, const float* relu_ref, void* dz_out, const void* c, const float* mean, const float* invstd,
                               const float* mask_scale, const float* mask_shift, long npix, int C, double* stats, void* stream, int io = 0) {
     hipStream_t st = (hipStream_t)stream;
-    if (!(io & SRBH_BN_STATS_CLEAN)) { if (int rc = zero_async(stats, (size_t)NSLOT * 2 * C * sizeof(double), st)) return rc; }
+    const bool clean = (io & SRBH_BN_STATS_CLEAN) != 0;
     io &= ~SRBH_BN_STATS_CLEAN;
     const bool gb = (io & SRBH_BN_G_B16) != 0, ch = (io & SRBH_BN_C_H16) != 0, ob = (io & SRBH_BN_OUT_B16) != 0, rb = (io & SRBH_BN_REF_BITS) != 0;
     const bool v4 = (C & 3) == 0 && (256 % (C >> 2)) == 0 && ((uintptr_t)g & (gb ? 7 : 15)) == 0 && ((uintptr_t)c & (ch ? 7 : 15)) == 0 &&
@@ -910,6 +910,9 @@ static int bn_bwd_reduce_impl(const void* g, const float* relu_ref, void* dz_out
                      (uintptr_t)mask_scale | (uintptr_t)mask_shift) & 15) == 0;
     SRBH_REQUIRE(!rb || (relu_ref && v4), "srbh_bn_bwd_reduce_io: SRBH_BN_REF_BITS needs relu_ref (the bit buffer) and the vector form");
     SRBH_REQUIRE(!io || v4, "srbh_bn_bwd_reduce: 16-bit tensors need the vector form (C %% 4 == 0, 256 %% (C/4) == 0, aligned)");
+    SRBH_REQUIRE(!relu_ref || v4, "srbh_bn_bwd_reduce_relu: needs the 16-byte form (C %% 4 == 0, 256 %% (C/4) == 0, aligned)");
+    // (the zero fill comes behind every refusal: a refused call writes nothing)
+    if (!clean) { if (int rc = zero_async(stats, (size_t)NSLOT * 2 * C * sizeof(double), st)) return rc; }
     if (v4) {
         const long n4 = npix * (C >> 2);
 #define SRBH_BNR(G_, C_, O_) hipLaunchKernelGGL((bn_bwd_reduce4_kernel<G_, C_, O_>), dim3(grid4_for(n4)), dim3(256), 2 * C * sizeof(float), st, \
@@ -929,7 +932,6 @@ static int bn_bwd_reduce_impl(const void* g, const float* relu_ref, void* dz_out
         }
 #undef SRBH_BNR
     } else {
-        SRBH_REQUIRE(!relu_ref, "srbh_bn_bwd_reduce_relu: needs the 16-byte form (C %% 4 == 0, aligned)");
         // a block size that is a multiple of C keeps every thread on ONE channel (register partial sums); with 256 threads and e.g.
         // C = 7 (the bias gradient of the 7-class output conv) every element went through an LDS atomic: 295 us for 117 MB
         const int bd = (256 % C == 0) ? 256 : (256 / C) * C;
@@ -975,6 +977,9 @@ extern "C" int srbh_bn_bwd_apply_io(const void* g, const void* c, const float* m
     const bool gb = (io & SRBH_BN_G_B16) != 0, ch = (io & SRBH_BN_C_H16) != 0, ob = (io & SRBH_BN_OUT_B16) != 0;
     SRBH_REQUIRE((io & ~7) == 0 && (C & 3) == 0 && (256 % (C >> 2)) == 0 && ((uintptr_t)g & (gb ? 7 : 15)) == 0 && ((uintptr_t)c & (ch ? 7 : 15)) == 0 &&
                  ((uintptr_t)out & (ob ? 7 : 15)) == 0, "srbh_bn_bwd_apply_io: needs the vector form (C %% 4 == 0, 256 %% (C/4) == 0, aligned)");
+    SRBH_REQUIRE(!mask_scale || mask_shift, "srbh_bn_bwd_apply_io: mask_scale needs mask_shift");
+    SRBH_REQUIRE((((uintptr_t)mean | (uintptr_t)invstd | (uintptr_t)coef | (uintptr_t)k1 | (uintptr_t)k2 | (uintptr_t)mask_scale | (uintptr_t)mask_shift) & 15) == 0,
+                 "srbh_bn_bwd_apply_io: 16-byte aligned per-channel vectors");
     const long n4 = npix * (C >> 2);
 #define SRBH_BNA(G_, C_, O_) hipLaunchKernelGGL((bn_bwd_apply4_kernel<G_, C_, O_>), dim3(grid4_for(n4)), dim3(256), 0, (hipStream_t)stream, \
                                                 g, c, mean, invstd, mask_scale, mask_shift, coef, k1, k2, out, n4, C)

@@ -116,43 +116,62 @@ def ref_conv64(x, w, b):
 
 
 # ---- memory contract of one C-ABI call: writes stay inside the outputs, inputs stay as they were -------------------------------------
-SLACK = 64          # floats of NaN on either side of every output
+SLACK = 64          # floats of NaN on either side of every output (256 bytes of guard for every other element type)
+SENTINEL = {torch.int64: 0x5AA5A55A5AA5A55A, torch.uint8: 0xA5}      # guard pattern of the integer types, which have no NaN
 
 
 class GuardedBuffers:
-    """the device buffers of one call: inputs with a clone to compare with afterwards, outputs carved out of NaN-filled storage"""
+    """the device buffers of one call: inputs with a clone to compare with afterwards, outputs carved out of guard-filled storage (NaN for
+    the float types, SENTINEL for int64 / uint8).  `offset` counts ELEMENTS of the buffer's dtype past a 16-byte boundary."""
 
     def __init__(self):
-        self.inputs, self.outputs = [], []
+        self.inputs, self.outputs, self.before = [], [], {}
 
     @staticmethod
-    def _carve(shape, offset):
+    def _guard(dtype):
+        return float("nan") if dtype.is_floating_point else SENTINEL[dtype]
+
+    @staticmethod
+    def _carve(shape, offset, dtype=torch.float32):
         n = math.prod(shape)
-        buf = torch.full((n + 2 * SLACK + 4,), float("nan"), device="cuda:0")
-        view = buf[SLACK + offset: SLACK + offset + n].view(shape)
-        assert buf.data_ptr() % 16 == 0 and view.data_ptr() % 16 == 4 * offset, (buf.data_ptr(), offset)
+        esz = torch.empty((), dtype=dtype).element_size()
+        slack = SLACK * 4 // esz
+        buf = torch.full((n + 2 * slack + 16 // esz,), GuardedBuffers._guard(dtype), dtype=dtype, device="cuda:0")
+        view = buf[slack + offset: slack + offset + n].view(shape)
+        assert buf.data_ptr() % 16 == 0 and view.data_ptr() % 16 == (esz * offset) % 16, (buf.data_ptr(), offset)
         return buf, view
 
-    def inp(self, t, offset=0):
-        """`t` on the device, `offset` floats past a 16-byte boundary"""
-        _, v = self._carve(tuple(t.shape), offset)
+    def inp(self, t, offset=0, dtype=torch.float32):
+        """`t` on the device as `dtype`, `offset` elements past a 16-byte boundary"""
+        _, v = self._carve(tuple(t.shape), offset, dtype)
         v.copy_(t)
         self.inputs.append((v, v.clone()))
         return v
 
-    def out(self, shape, offset=0, fill=None):
-        buf, v = self._carve(tuple(shape), offset)
+    def out(self, shape, offset=0, fill=None, dtype=torch.float32):
+        buf, v = self._carve(tuple(shape), offset, dtype)
         if fill is not None:
             v.copy_(fill)
         self.outputs.append((buf, v))
+        self.before[id(buf)] = None if fill is None else v.clone()
         return v
 
-    def verify(self):
+    @staticmethod
+    def _is_guard(t):
+        return t.isnan() if t.dtype.is_floating_point else t == SENTINEL[t.dtype]
+
+    def verify(self, written=True):
+        """inputs unchanged, guards intact, and every output element written (written = False: NO output element written -- a refused call)"""
         torch.cuda.synchronize()
         for v, c in self.inputs:
             assert torch.equal(v, c), "an input was written"
         for buf, v in self.outputs:
-            lo = (v.data_ptr() - buf.data_ptr()) // 4
-            assert lo >= SLACK and buf.numel() - lo - v.numel() >= SLACK
-            assert bool(buf[:lo].isnan().all()) and bool(buf[lo + v.numel():].isnan().all()), "a write outside the output"
-            assert not bool(v.isnan().any()), "an output element was left unwritten (or is NaN)"
+            slack = SLACK * 4 // buf.element_size()
+            lo = (v.data_ptr() - buf.data_ptr()) // buf.element_size()
+            assert lo >= slack and buf.numel() - lo - v.numel() >= slack
+            assert bool(self._is_guard(buf[:lo]).all()) and bool(self._is_guard(buf[lo + v.numel():]).all()), "a write outside the output"
+            if not written:
+                was = self.before[id(buf)]          # what the output held before the call: its guard pattern, or the `fill`
+                assert bool(self._is_guard(v).all()) if was is None else torch.equal(v, was), "a refused call wrote to an output"
+            elif v.dtype != torch.uint8:      # (a byte may equal its guard by chance)
+                assert not bool(self._is_guard(v).any()), "an output element was left unwritten (or is NaN)"
