@@ -939,6 +939,50 @@ int srbh_vgg_dist(const void* fx, const void* fg, int B, int chunks, int H, int 
  * dx = g / std[c] (/ 2 with range_norm) * *grad_output (a DEVICE scalar).  std_: 3 host floats or NULL. */
 int srbh_vgg_dx_nchw(const float* g, float* dx, int B, int H, int W, const float* std_, int range_norm, const float* grad_output, void* stream);
 
+/* ---- the discriminator's 4x4 / stride 2 / pad 1 convolutions (SR/rrdbnet_arch.py:262-264 conv1..conv3, used at :277-279) on ACT16 planes:
+ * srgan.UNetDiscriminatorSN.libsrbh_s2 = "f16" (csrc/srbh_disc.hip).  With xpad = x (C, H, W; C % 32 == 0, H and W even) in a
+ * zero ring of 1, the conv is a 2x2-tap VALID conv over the space-to-depth image of xpad -- no tap wasted, no strided read:
+ *   S[(2p+q) C + c][u][v]     = xpad[c][2u+p][2v+q]                   4C channels, (H/2+1) x (W/2+1)
+ *   W2[o][(2p+q) C + c][a][b] = w[o][c][2a+p][2b+q]                   a, b in {0, 1}
+ *   y[o][i][j]   = sum_{k,a,b} W2[o][k][a][b] S[k][i+a][j+b]          Ho x Wo = H/2 x W/2
+ *   dS[k][u][v]  = sum_{o,a,b} Wt[k][o][a][b] gpad[o][u+a][v+b]       Wt[k][o][a][b] = W2[o][k][1-a][1-b]; gpad = g in a zero ring of 1
+ *   dx           = depth-to-space(dS) with the ring cropped
+ *   dW2[o][k][a][b] = sum_{n,i,j} g[n][o][i][j] S[n][k][i+a][j+b]     (dw[o][c][2a+p][2b+q] = dW2[o][(2p+q) C + c][a][b])
+ * Arithmetic contract (rne16 = round to nearest even to fp16, bf16 likewise; every product of two 16-bit operands is exact in fp32, fp32
+ * accumulation in any order, fp32 results unrounded):
+ *   forward          y  = conv(rne16(x), rne16(w))
+ *   data gradient    dx = conv^T(bf16(g), bf16(w))
+ *   weight gradient  dw = sum bf16(g) * bf16(rne16(x))    fixed summation order, no atomics: two calls on the same input are bit-equal
+ * No entry below launches anything when an argument check fails. */
+/* x fp32 NHWC (B, H, W, C) -> the 4C / 32 chunk planes of S (phase (p, q) fills the C / 32 planes from (2p+q) C / 32 on), fp16 or (bf16 != 0)
+ * bf16, RNE.  The whole (H/2+1) x (W/2+1) interior is written, the pad-derived zeros included; plane borders and read slack are those of
+ * srbh_act16_bytes(B, 4 C, H/2+1, W/2+1) (zeroed once by whoever allocates the buffer). */
+int srbh_s2d_nhwc32_to_act16(const float* x, void* planes, int B, int C, int H, int W, int bf16, void* stream);
+/* g fp32 NHWC (B, H, W, C) -> C / 32 chunk planes with interior (H+2) x (W+2): the data at (1, 1), the ring written as zeros (gpad above);
+ * buffer: srbh_act16_bytes(B, C, H+2, W+2). */
+int srbh_nhwc32_to_act16_framed(const float* x, void* planes, int B, int C, int H, int W, int bf16, void* stream);
+/* the weight packs of the 2x2-tap form: [input chunk][tap a*2+b][k-step][cout / 32][lane][8], 8 KiB per (chunk, 32 output channels).
+ * srbh_pack_conv4x4s2: w fp32 OIHW [O][C][4][4]; transpose_flip = 0: W2, a (cout = O, cin = 4C) pack; 1: Wt, a (cout = 4C, cin = O) pack; RNE to
+ * fp16 or (bf16 != 0) bf16.  Both have srbh_wpack2x2_bytes(O, 4 C) bytes.  _pair: W2 in fp16 and Wt in bf16 in one launch (spectral norm
+ * rewrites the weight on every training forward). */
+size_t srbh_wpack2x2_bytes(int cout, int cin);
+int srbh_pack_conv4x4s2(const float* w, int O, int C, int transpose_flip, int bf16, void* packed, void* stream);
+int srbh_pack_conv4x4s2_pair(const float* w, int O, int C, void* w2_f16, void* wt_b16, void* stream);
+/* the 2x2-tap VALID form of srbh_wconv3x3 (same kernel body, taps dy, dx in {1, 2} of its pad-1 indexing; 8 weight fragments per chunk and
+ * 32 output channels instead of 18): out32[n][i][j][o] = sum_{k,a,b} W[o][k][a][b] in[n][k][i+a][j+b] for i < H, j < W from planes whose
+ * interior is (H+1) x (W+1) (buffer geometry of srbh_act16_bytes(B, 32 in_chunks_total, H+1, W+1)).  a->w: a srbh_pack_conv4x4s2 pack of
+ * (cout, 32 in_chunks); bf16 selects the operand format of planes and pack.  cout % 64 == 0, in_chunks >= 1, out32_c == cout; bias, relu,
+ * mask16, add16 and out16 must be 0 / NULL (the module applies LeakyReLU outside). */
+int srbh_wconv2x2(const srbh_wconv3x3_args* a, void* stream);
+/* ds fp32 NHWC (B, H/2+1, W/2+1, 4C) -> dx fp32 NHWC (B, H, W, C): dx[y][x][c] = ds[(y+1)/2][(x+1)/2][(2 ((y+1)%2) + (x+1)%2) C + c], the
+ * exact inverse permutation of S with the ring dropped. */
+int srbh_d2s_nhwc32(const float* ds, float* dx, int B, int C, int H, int W, void* stream);
+/* dw fp32 OIHW [O][C][4][4] from the saved fp16 planes of S (srbh_s2d_nhwc32_to_act16 of the (B, 2 Ho, 2 Wo, C) input) and the framed bf16
+ * planes of g (srbh_nhwc32_to_act16_framed of (B, Ho, Wo, O)); S is re-rounded fp16 -> bf16 while staged, as srbh_act16_wgrad_b16 does.
+ * O % 64 == 0, C % 32 == 0.  ws: srbh_wgrad4x4s2_ws_bytes bytes, no initialisation needed. */
+size_t srbh_wgrad4x4s2_ws_bytes(int O, int C, int B, int Ho, int Wo);
+int srbh_wgrad4x4s2_b16(const void* s_planes, const void* g_planes, int B, int C, int O, int Ho, int Wo, float* dw, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -105,11 +105,20 @@ __device__ __forceinline__ int xcd_remap(int bid, int n) {
 // BF = 2: bf16 operands as BF = 1, the 16-bit output rounded to fp16 (the bf16 inference trunk's last conv5: its planes leave for conv_body).
 // WIDE = 1: p is a WKParams; weight fragments are fetched at the wide pack's stride, the epilogue is ReLU (slope 0) instead of LeakyReLU --
 // mask (saved plane > 0 ? v : 0), then the addend planes, then ReLU -- and the fp32 output takes the slice's channel offset.
-template <int CB, int UPS, int ABL, int PERSIST, int BF = 0, int WIDE = 0>
+// T2 = 1 (srbh_wconv2x2, the discriminator's 4x4 stride-2 convs on space-to-depth planes): the 2x2-tap VALID form -- only the taps dy, dx in
+// {1, 2} of the pad-1 indexing are walked (out[Y][X] = sum in_interior[Y + a][X + b], a, b in {0, 1}: the input interior is (H+1) x (W+1)),
+// a chunk stages 8 x CB weight fragments ([tap a*2+b][k-step][mb]) and runs four (k-step, dx) groups of 8 x CB MFMAs.  KT / NG / NF below are
+// 3 / 6 / 18 x CB for every other form: their code is what it was.
+template <int CB, int UPS, int ABL, int PERSIST, int BF = 0, int WIDE = 0, int T2 = 0>
 __device__ __forceinline__ void conv_tile(const KParams& p, char* smem, const int img, const int Y0, const int X0,
                                           unsigned long long* tstamp) {
     using G = TileGeo<UPS>;
-    constexpr int W_B = 18 * 1024 * CB;  // weight bytes per input chunk
+    static_assert(!T2 || (WIDE && !UPS), "the 2x2-tap form is a wide, non-upsampling form");
+    constexpr int KT = T2 ? 2 : 3;       // taps per axis
+    constexpr int T0 = T2 ? 1 : 0;       // first tap of the pad-1 indexing
+    constexpr int NG = 2 * KT;           // (k-step, dx) groups per chunk
+    constexpr int NF = 2 * KT * KT * CB; // weight fragments per input chunk
+    constexpr int W_B = NF * 1024;       // weight bytes per input chunk
     constexpr int STAGE_B = G::IN_B + W_B;
 
     const int tid = threadIdx.x;
@@ -134,7 +143,7 @@ __device__ __forceinline__ void conv_tile(const KParams& p, char* smem, const in
     const char* wsrc = p.w + lane * 16;
 
     // weights: 18*CB fragments of 1 KiB per chunk, fragment f is copied by wave f%4
-    constexpr int WFR = (18 * CB + 3) / 4;       // fragments per wave per chunk
+    constexpr int WFR = (NF + 3) / 4;            // fragments per wave per chunk
     constexpr int WPP = (WFR + 5) / 6;           // ... per pipeline part
     constexpr int JPP = (G::NJ + 5) / 6;         // input LDS-DMA instructions per pipeline part
 
@@ -156,7 +165,7 @@ __device__ __forceinline__ void conv_tile(const KParams& p, char* smem, const in
 #pragma unroll
             for (int kk = 0; kk < WPP; ++kk) {
                 const int f = wave + 4 * (part * WPP + kk);
-                if (part * WPP + kk < WFR && f < 18 * CB)
+                if (part * WPP + kk < WFR && f < NF)
                     __builtin_amdgcn_global_load_lds(GPTR(ws + ((f / CB) * wp.w_nmb + f % CB) * 1024), LPTR(wdst + f * 1024), 16, 0, 0);
             }
             return;
@@ -165,16 +174,16 @@ __device__ __forceinline__ void conv_tile(const KParams& p, char* smem, const in
 #pragma unroll
         for (int kk = 0; kk < WPP; ++kk) {
             const int f = wave + 4 * (part * WPP + kk);
-            if (part * WPP + kk < WFR && f < 18 * CB)
+            if (part * WPP + kk < WFR && f < NF)
                 __builtin_amdgcn_global_load_lds(GPTR(ws + f * 1024), LPTR(wdst + f * 1024), 16, 0, 0);
         }
     };
 
     // ---- per-lane operand addresses inside a stage
-    int aoff[3][2];
+    int aoff[KT][2];
 #pragma unroll
-    for (int dx = 0; dx < 3; ++dx) {
-        const int pc = UPS ? (((wc * 32 + l31 + dx - 1) >> 1) + 1) : (wc * 32 + l31 + dx);
+    for (int dx = 0; dx < KT; ++dx) {
+        const int pc = UPS ? (((wc * 32 + l31 + dx - 1) >> 1) + 1) : (wc * 32 + l31 + dx + T0);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
             aoff[dx][ks] = wr * (UPS ? 2 : 4) * G::ROW_B + pc * PIX_B + (((ks * 2 + hi) ^ ((pc >> 2) & 3)) << 4);
@@ -191,11 +200,11 @@ __device__ __forceinline__ void conv_tile(const KParams& p, char* smem, const in
 
     // fragment registers, double buffered over the six (k-step, dx) groups of a chunk
     half8 P[2][G::NP];
-    half8 A[2][3][CB];
+    half8 A[2][KT][CB];
     auto load_group = [&](const char* sb, int g, int set) {
-        const int ks = g / 3, dx = g - ks * 3;
+        const int ks = g / KT, dx = g - ks * KT;
 #pragma unroll
-        for (int r = 0; r < G::NP; ++r) {
+        for (int r = T0; r < G::NP; ++r) {
             if (ABL == 4) {
                 P[set][r] = half8{(_Float16)lane, 1, 2, 3, 4, 5, 6, (_Float16)(r + dx)};
                 asm volatile("" : "+v"(P[set][r]));
@@ -204,27 +213,27 @@ __device__ __forceinline__ void conv_tile(const KParams& p, char* smem, const in
             }
         }
 #pragma unroll
-        for (int dy = 0; dy < 3; ++dy)
+        for (int dy = 0; dy < KT; ++dy)
 #pragma unroll
             for (int mb = 0; mb < CB; ++mb) {
                 if (ABL == 4) {
                     A[set][dy][mb] = half8{(_Float16)lane, 1, 2, 3, 4, 5, 6, (_Float16)(mb + dy)};
                     asm volatile("" : "+v"(A[set][dy][mb]));
                 } else {
-                    A[set][dy][mb] = *(const half8*)(sb + woff + ((((dy * 3 + dx) * 2 + ks) * CB + mb) << 10));
+                    A[set][dy][mb] = *(const half8*)(sb + woff + ((((dy * KT + dx) * 2 + ks) * CB + mb) << 10));
                 }
             }
     };
 
-    constexpr int NREAD = G::NP + 3 * CB;   // ds_read_b128 per group
-    constexpr int NMFMA = 12 * CB;          // MFMAs per group
+    constexpr int NREAD = G::NP - T0 + KT * CB;   // ds_read_b128 per group
+    constexpr int NMFMA = 4 * KT * CB;            // MFMAs per group
     // ONE code path for every chunk: per-variant copies of this body made the compiler shuffle all accumulators at the
     // join.  The LDS-DMA slices of chunk c+1 sit behind a wave-uniform branch at the head of each MFMA group.
     auto chunk_body = [&](const bool more, int c) {
         const char* sb = smem + (c & 1) * STAGE_B;
         load_group(sb, 0, 0);
 #pragma unroll
-        for (int g = 0; g < 6; ++g) {
+        for (int g = 0; g < NG; ++g) {
             // all six DMA slices of chunk c+1 go out in the first two MFMA groups: a chunk cannot end before its LAST
             // slice has landed (issue time + L2 latency), spreading them over all six groups made every chunk latency-bound
             if (more && ABL != 2 && g < 2) {
@@ -232,12 +241,12 @@ __device__ __forceinline__ void conv_tile(const KParams& p, char* smem, const in
                 stage_part(c + 1, (c + 1) & 1, 3 * g + 1);
                 stage_part(c + 1, (c + 1) & 1, 3 * g + 2);
             }
-            if (g + 1 < 6) load_group(sb, g + 1, (g + 1) & 1);   // next group's LDS reads fly under this group's MFMAs
+            if (g + 1 < NG) load_group(sb, g + 1, (g + 1) & 1);   // next group's LDS reads fly under this group's MFMAs
 #pragma unroll
-            for (int dy = 0; dy < 3; ++dy) {
+            for (int dy = 0; dy < KT; ++dy) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const int pr = UPS ? (((i + dy - 1) >> 1) + 1) : (i + dy);
+                    const int pr = UPS ? (((i + dy - 1) >> 1) + 1) : (i + dy + T0);
 #pragma unroll
                     for (int mb = 0; mb < CB; ++mb)
                         if constexpr (BF)
@@ -250,7 +259,7 @@ __device__ __forceinline__ void conv_tile(const KParams& p, char* smem, const in
 #if SRBH_SCHED_HINTS
             // pin the interleave: one ds_read behind each of the first NREAD MFMAs, then the rest
             if (g == 0) __builtin_amdgcn_sched_group_barrier(0x100, NREAD, 0);
-            if (g + 1 < 6) {
+            if (g + 1 < NG) {
 #pragma unroll
                 for (int k = 0; k < NREAD; ++k) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -528,6 +537,22 @@ __global__ __launch_bounds__(256, 1) void wconv3x3_kernel(const WKParams p0) {
     const int trem = t - img * p.tiles_per_img;
     const int ty = trem / p.tiles_x, tx = trem - ty * p.tiles_x;
     conv_tile<CB, 0, 0, 0, BF, 1>(p, smem, img, ty * TILE_H, tx * TILE_W, tstamp);
+}
+
+// The 2x2-tap valid form of the wide kernel (srbh_wconv2x2): the same grid and slice shifts, fp32 NHWC output only.
+template <int CB, int BF>
+__global__ __launch_bounds__(256, 1) void wconv2x2_kernel(const WKParams p0) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    unsigned long long tstamp[8];
+    const int l = xcd_remap(blockIdx.x, p0.nblocks);
+    const int t = l / p0.nslice, s = l - t * p0.nslice;
+    WKParams p = p0;
+    p.w = p0.w + (long)s * CB * 1024;
+    p.out32_c0 = s * CB * 32;
+    const int img = t / p.tiles_per_img;
+    const int trem = t - img * p.tiles_per_img;
+    const int ty = trem / p.tiles_x, tx = trem - ty * p.tiles_x;
+    conv_tile<CB, 0, 0, 0, BF, 1, 1>(p, smem, img, ty * TILE_H, tx * TILE_W, tstamp);
 }
 
 }  // namespace srbh_k
