@@ -983,6 +983,45 @@ int srbh_d2s_nhwc32(const float* ds, float* dx, int B, int C, int H, int W, void
 size_t srbh_wgrad4x4s2_ws_bytes(int O, int C, int B, int Ho, int Wo);
 int srbh_wgrad4x4s2_b16(const void* s_planes, const void* g_planes, int B, int C, int O, int Ho, int Wo, float* dw, void* ws, void* stream);
 
+/* ---- the discriminator's wide 3x3 / stride 1 / pad 1 convolutions with LeakyReLU (SR/rrdbnet_arch.py:265-269 conv4..conv8, used at :285-300:
+ * act(conv_k(t)), bias-free, slope 0.2) on ACT16 planes: srgan.UNetDiscriminatorSN.libsrbh_wide = "f16" (csrc/srbh_disc3.hip).
+ *   z  = conv(x, w)                 y = z >= 0 ? z : 0.2 z
+ *   g' = g * (y > 0 ? 1 : 0.2)      (torch's leaky_relu backward rule on the saved output)
+ *   dx[c][i][j]    = sum_{o,a,b} Wt[c][o][a][b] g'[o][i+a-1][j+b-1]       Wt[c][o][a][b] = w[o][c][2-a][2-b]
+ *   dw[o][c][a][b] = sum_{n,i,j} g'[n][o][i][j] x[n][c][i+a-1][j+b-1]     (zero outside the image)
+ * Arithmetic contract, that of the 4x4 stride-2 block above (rne16 = round to nearest even to fp16, bf16 likewise; every product of two 16-bit
+ * operands is exact in fp32, fp32 accumulation in any order, fp32 results unrounded):
+ *   forward          y  = lrelu(conv(rne16(x), rne16(w))), the one product of the LeakyReLU rounded in fp32
+ *   staged gradient  g' = bf16(g * (y > 0 ? 1 : slope)), the product formed in fp32
+ *   data gradient    dx = conv(g', bf16(Wt))
+ *   weight gradient  dw = sum g' * bf16(rne16(x))      fixed summation order, no atomics: two calls on the same input (and the same walker
+ *                                                       count) are bit-equal
+ * No entry below launches anything when an argument check fails. */
+/* srbh_wconv3x3 with the forward LeakyReLU (slope 0.2, v >= 0 ? v : v * 0.2f in fp32) as the last step of the epilogue, in front of the 16-bit
+ * and fp32 stores: the same kernel body, one more compile-time form.  bias, relu, mask16 and add16 must be 0 / NULL; everything else as
+ * srbh_wconv3x3 (cout 32 or a multiple of 64, out16 and / or out32, bf16 selects the operand format). */
+int srbh_wconv3x3_lrelu(const srbh_wconv3x3_args* a, void* stream);
+/* g, y fp32 NHWC (B, H, W, C), y the saved output of the forward -> the C / 32 chunk planes of rne(g * (y > 0 ? 1 : slope)) as bf16 (bf16 != 0)
+ * or fp16; interior only: the zero border of a buffer of srbh_act16_bytes(B, C, H, W) (zeroed once by whoever allocates it) is kept.
+ * C % 32 == 0; one read of each input. */
+int srbh_nhwc32_to_act16_lrelu_bwd(const float* g, const float* y, void* planes, int B, int C, int H, int W, float slope, int bf16, void* stream);
+/* both packs of one weight in one launch (spectral norm rewrites the weight on every training forward): w fp32 OIHW [cout][cin][3][3];
+ * w_f16 = the WPACK16 of w in fp16, the bits of srbh_pack_conv3x3_f16(w, cout, cin); wt_b16 = the WPACK16 of Wt (above) in bf16, the bits of
+ * srbh_pack_conv3x3_b16(Wt, cin, cout).  cout % 32 == 0, cin % 32 == 0: both packs have srbh_wpack16_bytes(cout, cin) bytes. */
+int srbh_pack_conv3x3_pair(const float* w_oihw, int cout, int cin, void* w_f16, void* wt_b16, void* stream);
+/* dw fp32 OIHW [cout][cin][3][3] from the fp16 planes the forward staged (x: chunk planes 0 .. cin / 32 - 1 of a buffer of x_chunks_total
+ * planes, re-rounded fp16 -> bf16 (RNE) while staged, as srbh_act16_wgrad_b16 and srbh_wgrad4x4s2_b16 do; the planes' zero border is the padding)
+ * and the bf16 planes of g' (srbh_nhwc32_to_act16_lrelu_bwd).  One launch covers all output channels: a workgroup owns a 64 (o) x 32 (c) x 9
+ * block and walks the 8 x 64 tiles blockIdx.x, + walkers, ...; its partial sums go to its own slot of ws, a second kernel folds the slots in
+ * walker order.  cin % 32 == 0; cout 32 or a multiple of 64.  ws: srbh_wgrad3x3_ws_bytes bytes (0 for a shape the entry refuses), no
+ * initialisation needed.  Nothing outside the planes' borders is read. */
+size_t srbh_wgrad3x3_ws_bytes(int cout, int cin, int B, int H, int W);
+int srbh_wgrad3x3_b16(const void* x_planes, int x_chunks_total, int cin, const void* g_planes, int g_chunks_total, int cout, int B, int H, int W,
+                      float* dw, void* ws, void* stream);
+/* test hook: at most `cap` walkers per block in srbh_wgrad3x3_b16 / _ws_bytes from now on (process-wide); 0 restores the default (one workgroup
+ * per compute unit over all blocks).  Returns the previous value.  Small shapes need it to give a workgroup more than one tile. */
+int srbh_wgrad3x3_walkers_cap(int cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,7 +17,7 @@ CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(ROOT, "include")
 LIB_PATH = os.path.join(_HERE, "libsrbh.so")
 _DEV_LIB = os.environ.get("SRBH_LIB_PATH")      # developer A/B only (tools/ab_variants.sh): load another build of the same ABI
-SOURCES = ["srbh_conv3x3.hip", "srbh_aux.hip", "srbh_rrdbnet.hip", "srbh_ptrunk.hip", "srbh_trunk_wgrad.hip", "srbh_ptail.hip", "srbh_ptail_split.hip", "srbh_head.hip", "srbh_head_bwd.hip", "srbh_mosaic.hip", "srbh_loader.hip", "srbh_loss.hip", "srbh_sr_metrics.hip", "srbh_eval.hip", "srbh_dwconv.hip", "srbh_mbconv.hip", "srbh_pwconv.hip", "srbh_dconv.hip", "srbh_optim.hip", "srbh_vgg.hip", "srbh_disc.hip"]
+SOURCES = ["srbh_conv3x3.hip", "srbh_aux.hip", "srbh_rrdbnet.hip", "srbh_ptrunk.hip", "srbh_trunk_wgrad.hip", "srbh_ptail.hip", "srbh_ptail_split.hip", "srbh_head.hip", "srbh_head_bwd.hip", "srbh_mosaic.hip", "srbh_loader.hip", "srbh_loss.hip", "srbh_sr_metrics.hip", "srbh_eval.hip", "srbh_dwconv.hip", "srbh_mbconv.hip", "srbh_pwconv.hip", "srbh_dconv.hip", "srbh_optim.hip", "srbh_vgg.hip", "srbh_disc.hip", "srbh_disc3.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # NOTE: `-mllvm -amdgpu-mfma-vgpr-form=1` (accumulators in VGPRs: no v_accvgpr copies at K-loop back-edges).  Round 1 saw the
 # first persistent trunk kernel produce non-deterministic garbage with it; round 3 re-ran it on the current kernel (ptrunk3:
@@ -379,6 +379,12 @@ SIGNATURES = {
     "srbh_d2s_nhwc32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "srbh_wgrad4x4s2_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "srbh_wgrad4x4s2_b16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "srbh_wconv3x3_lrelu": (_i, [C.POINTER(WConvArgs), _vp]),
+    "srbh_nhwc32_to_act16_lrelu_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp]),
+    "srbh_pack_conv3x3_pair": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "srbh_wgrad3x3_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "srbh_wgrad3x3_b16": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "srbh_wgrad3x3_walkers_cap": (_i, [_i]),
     "srbh_trunk_timing": (_i, [_i]),
     "srbh_trunk_last_ms": (_i, [C.POINTER(C.c_float)]),
     "srbh_trunk_kernel_name": (C.c_char_p, []),

@@ -109,11 +109,14 @@ __device__ __forceinline__ int xcd_remap(int bid, int n) {
 // {1, 2} of the pad-1 indexing are walked (out[Y][X] = sum in_interior[Y + a][X + b], a, b in {0, 1}: the input interior is (H+1) x (W+1)),
 // a chunk stages 8 x CB weight fragments ([tap a*2+b][k-step][mb]) and runs four (k-step, dx) groups of 8 x CB MFMAs.  KT / NG / NF below are
 // 3 / 6 / 18 x CB for every other form: their code is what it was.
-template <int CB, int UPS, int ABL, int PERSIST, int BF = 0, int WIDE = 0, int T2 = 0>
+// LR = 1 (srbh_wconv3x3_lrelu, the discriminator's conv4..conv8): the wide epilogue ends with the forward LeakyReLU of the non-wide form,
+// v >= 0 ? v : 0.2 v in fp32, in front of the stores; with LR = 0 the branch does not exist.
+template <int CB, int UPS, int ABL, int PERSIST, int BF = 0, int WIDE = 0, int T2 = 0, int LR = 0>
 __device__ __forceinline__ void conv_tile(const KParams& p, char* smem, const int img, const int Y0, const int X0,
                                           unsigned long long* tstamp) {
     using G = TileGeo<UPS>;
     static_assert(!T2 || (WIDE && !UPS), "the 2x2-tap form is a wide, non-upsampling form");
+    static_assert(!LR || (WIDE && !T2), "the LeakyReLU epilogue form is a wide 3x3 form");
     constexpr int KT = T2 ? 2 : 3;       // taps per axis
     constexpr int T0 = T2 ? 1 : 0;       // first tap of the pad-1 indexing
     constexpr int NG = 2 * KT;           // (k-step, dx) groups per chunk
@@ -422,6 +425,13 @@ __device__ __forceinline__ void conv_tile(const KParams& p, char* smem, const in
                                 v1[q] = v1[q] > 0.f ? v1[q] : 0.f;
                             }
                         }
+                        if constexpr (LR) {
+#pragma unroll
+                            for (int q = 0; q < 4; ++q) {
+                                v0[q] = v0[q] >= 0.f ? v0[q] : v0[q] * 0.2f;
+                                v1[q] = v1[q] >= 0.f ? v1[q] : v1[q] * 0.2f;
+                            }
+                        }
                     }
                     if (!WIDE && p.lrelu) {
 #pragma unroll
@@ -553,6 +563,23 @@ __global__ __launch_bounds__(256, 1) void wconv2x2_kernel(const WKParams p0) {
     const int trem = t - img * p.tiles_per_img;
     const int ty = trem / p.tiles_x, tx = trem - ty * p.tiles_x;
     conv_tile<CB, 0, 0, 0, BF, 1, 1>(p, smem, img, ty * TILE_H, tx * TILE_W, tstamp);
+}
+
+// The LeakyReLU form of the wide kernel (srbh_wconv3x3_lrelu): wconv3x3_kernel with conv_tile<.., LR = 1>.
+template <int CB, int BF>
+__global__ __launch_bounds__(256, 1) void wconv3x3_lrelu_kernel(const WKParams p0) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    unsigned long long tstamp[8];
+    const int l = xcd_remap(blockIdx.x, p0.nblocks);
+    const int t = l / p0.nslice, s = l - t * p0.nslice;
+    WKParams p = p0;
+    p.w = p0.w + (long)s * CB * 1024;
+    if (p0.out16) p.out16 = p0.out16 + (long)s * CB * p0.out16_plane_b;
+    p.out32_c0 = s * CB * 32;
+    const int img = t / p.tiles_per_img;
+    const int trem = t - img * p.tiles_per_img;
+    const int ty = trem / p.tiles_x, tx = trem - ty * p.tiles_x;
+    conv_tile<CB, 0, 0, 0, BF, 1, 0, 1>(p, smem, img, ty * TILE_H, tx * TILE_W, tstamp);
 }
 
 }  // namespace srbh_k

@@ -661,6 +661,9 @@ class RealESRGAN:
         # Its three 4x4 stride-2 convs (conv1..conv3) as 2x2-tap convs on space-to-depth ACT16 planes (srgan._DiscConvS2Fn, csrc/srbh_disc.hip):
         # opt-in, SRBH_SR_DISC_S2=libsrbh, in the 16-bit operand modes only (there is no exact-fp32 form, for the reason above).
         self.net_d.libsrbh_s2 = "f16" if (on_gpu and os.environ.get("SRBH_SR_DISC_S2", "") == "libsrbh" and RA._mixed()) else None
+        # act(conv4..conv8) (3x3 stride 1, 64..512 channels) as one plane function per conv (srgan._DiscConvWideFn, csrc/srbh_disc3.hip): opt-in,
+        # SRBH_SR_DISC_WIDE=libsrbh, in the 16-bit operand modes only.
+        self.net_d.libsrbh_wide = "f16" if (on_gpu and os.environ.get("SRBH_SR_DISC_WIDE", "") == "libsrbh" and RA._mixed()) else None
         # The VGG19 stack behind the perceptual term on libsrbh's 16-bit kernels (srgan._PerceptualFn): opt-in, SRBH_SR_VGG=libsrbh, for an
         # srgan.PerceptualLoss on the device only (a foreign plug-in module keeps its own forward).
         from .srgan import PerceptualLoss as _PL

@@ -20,7 +20,8 @@ __all__ = ["UNetDiscriminatorSN", "filter2D", "USMSharp", "GANLoss"]
 # They run on the head's convolution kernels (csrc/srbh_head.hip, srbh_head_bwd.hip: forward, data gradient = the forward kernel on transposed +
 # flipped weights, weight gradient as a GEMM over pixels) in slices of <= 64 output channels (the kernels' limit), in the precision of the SR-stage
 # mode: exact fp32, or fp16 forward / bf16 gradient operands with fp32 accumulation (`precision`).  The three 4x4 stride-2 convs (unless
-# `libsrbh_s2` is set, below), LeakyReLU and the skip additions stay stock device ops.  The spectral-norm reparametrisation is torch's own: the hook computes
+# `libsrbh_s2` is set, below), LeakyReLU and the skip additions stay stock device ops; with `libsrbh_wide` set, conv4..conv8 leave these kernels for
+# the wide plane kernels with the LeakyReLU in their epilogue (further below).  The spectral-norm reparametrisation is torch's own: the hook computes
 # `weight = weight_orig / sigma` (with its power iteration in training), the convolution takes that tensor and returns its gradient.
 # UNetDiscriminatorSN.libsrbh selects it; the trainer turns it on with the generator's 16-bit operand modes (RealESRGAN.optimize_parameters: 57.5 ->
 # 52.2 ms per iteration at batch 8, profiles/r05cs).  Restricting it to the <= 64-channel convs (one launch each) gained nothing.
@@ -217,6 +218,91 @@ def _disc_conv4x4s2(conv, x):
     return _DiscConvS2Fn.apply(x, conv.weight)
 
 
+# ---- act(conv4..conv8) on ACT16 planes (UNetDiscriminatorSN.libsrbh_wide = "f16") ------------------------------------------------------------
+# conv4..conv8 (SR/rrdbnet_arch.py:265-269, used at :285-300) are 3x3 / stride 1 / pad 1 without bias, 64..512 channels, each followed by
+# LeakyReLU(0.2).  One autograd function per conv runs conv + activation on csrc/srbh_disc3.hip and the wide conv of the trunk's family
+# (DESIGN.md 3.21): the input staged once as fp16 planes, one launch for all output channels with the LeakyReLU in its epilogue; in the backward
+# the gradient staged once as bf16 planes with the LeakyReLU derivative applied, the data gradient as the same wide conv on the transposed +
+# flipped pack, the weight gradient in one launch (srbh_wgrad3x3_b16).  fp16 operands forward, bf16 operands in both gradients, fp32
+# accumulation (include/srbh.h states the contract).  Both packs are made per call, in one launch (spectral norm).
+class _DiscConvWideFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight):
+        import ctypes as C
+        from . import _lib
+        from . import hrfuse as H
+        L, sp = _lib.lib(), _lib.stream_ptr
+        xn = H.to_nhwc(x.detach().float())
+        w = weight.detach().float().contiguous()
+        B, Cc, Hh, Ww = xn.shape
+        O = w.shape[0]
+        dev = x.device
+        with torch.cuda.device(dev):
+            X = torch.zeros(L.srbh_act16_bytes(B, Cc, Hh, Ww), dtype=torch.uint8, device=dev)
+            _lib.check(L.srbh_nhwc32_to_act16(xn.data_ptr(), X.data_ptr(), B, Cc, Hh, Ww, Cc // 32, 0, 1.0, 0, sp()), "nhwc32_to_act16(disc wide)")
+            nb = L.srbh_wpack16_bytes(O, Cc)
+            wf, wt = torch.empty(nb, dtype=torch.uint8, device=dev), torch.empty(nb, dtype=torch.uint8, device=dev)
+            _lib.check(L.srbh_pack_conv3x3_pair(w.data_ptr(), O, Cc, wf.data_ptr(), wt.data_ptr(), sp()), "pack_conv3x3_pair(disc wide)")
+            y = H.empty_nhwc(B, O, Hh, Ww, dev)
+            a = _lib.WConvArgs()
+            a.in_, a.in_chunks_total, a.in_chunk0, a.in_chunks = X.data_ptr(), Cc // 32, 0, Cc // 32
+            a.w, a.cout, a.B, a.H, a.W = wf.data_ptr(), O, B, Hh, Ww
+            a.out32, a.out32_c = y.data_ptr(), O
+            _lib.check(L.srbh_wconv3x3_lrelu(C.byref(a), sp()), "wconv3x3_lrelu(disc fwd)")
+        ctx.save_for_backward(X, y, wt)
+        ctx.geo = (B, Cc, O, Hh, Ww)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        import ctypes as C
+        from . import _lib
+        from . import hrfuse as H
+        L, sp = _lib.lib(), _lib.stream_ptr
+        X, y, wt = ctx.saved_tensors
+        B, Cc, O, Hh, Ww = ctx.geo
+        dev = g.device
+        dx = dw = None
+        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return None, None
+        with torch.cuda.device(dev):
+            gn = H.to_nhwc(g.float())
+            G = torch.zeros(L.srbh_act16_bytes(B, O, Hh, Ww), dtype=torch.uint8, device=dev)
+            _lib.check(L.srbh_nhwc32_to_act16_lrelu_bwd(gn.data_ptr(), y.data_ptr(), G.data_ptr(), B, O, Hh, Ww, 0.2, 1, sp()), "nhwc32_to_act16_lrelu_bwd(disc)")
+            if ctx.needs_input_grad[0]:
+                dx = H.empty_nhwc(B, Cc, Hh, Ww, dev)
+                a = _lib.WConvArgs()
+                a.in_, a.in_chunks_total, a.in_chunk0, a.in_chunks = G.data_ptr(), O // 32, 0, O // 32
+                a.w, a.cout, a.B, a.H, a.W, a.bf16 = wt.data_ptr(), Cc, B, Hh, Ww, 1
+                a.out32, a.out32_c = dx.data_ptr(), Cc
+                _lib.check(L.srbh_wconv3x3(C.byref(a), sp()), "wconv3x3(disc dgrad)")
+            if ctx.needs_input_grad[1]:
+                dw = torch.empty((O, Cc, 3, 3), dtype=torch.float32, device=dev)
+                ws = torch.empty(L.srbh_wgrad3x3_ws_bytes(O, Cc, B, Hh, Ww) // 4, dtype=torch.float32, device=dev)
+                _lib.check(L.srbh_wgrad3x3_b16(X.data_ptr(), Cc // 32, Cc, G.data_ptr(), O // 32, O, B, Hh, Ww, dw.data_ptr(), ws.data_ptr(), sp()),
+                           "wgrad3x3_b16(disc)")
+        return dx, dw
+
+
+def _disc_conv3x3_act(conv, x, stock):
+    """leaky_relu(conv(x), 0.2) of a wide 3x3 stride-1 discriminator conv on libsrbh (_DiscConvWideFn), under the hook protocol of
+    _disc_conv4x4s2: spectral norm's pre-hook is called by hand, a module with any other hook takes `stock(conv, x)` -- what the module did
+    without this mode.  So does every conv or input outside what the kernels are meant for (bias, other geometry, in_channels % 64,
+    out_channels % 64, CPU tensors): % 64 is the module's gate as in _disc_conv4x4s2, it keeps the 8-feature net of fixture g14 on what it runs
+    today (the kernels themselves take in_channels % 32 and 32 output channels, include/srbh.h)."""
+    from torch.nn.utils.spectral_norm import SpectralNorm
+    ok = (isinstance(conv, nn.Conv2d) and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)
+          and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None and conv.padding_mode == "zeros"
+          and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0 and x.dim() == 4 and x.is_cuda)
+    pre = list(conv._forward_pre_hooks.values())
+    if (not ok or any(not isinstance(h, SpectralNorm) for h in pre) or conv._forward_hooks or conv._backward_hooks or conv._backward_pre_hooks
+            or getattr(conv, "_forward_pre_hooks_with_kwargs", None) or getattr(conv, "_forward_hooks_with_kwargs", None)):
+        return stock(conv, x)
+    for hook in pre:
+        hook(conv, (x,))
+    return _DiscConvWideFn.apply(x, conv.weight)
+
+
 class _Bilinear2xFn(torch.autograd.Function):
     """F.interpolate(scale_factor=2, mode="bilinear", align_corners=False) on a device tensor through srbh_bilinear2x_nhwc_f32 (the stock backward
     scatters with atomics: 4.5 ms of a 52 ms trainer iteration at batch 8)"""
@@ -263,6 +349,7 @@ class UNetDiscriminatorSN(nn.Module):
 
     libsrbh = None          # None: stock convolutions; "f32" / "f16": the 3x3 stride-1 convs on libsrbh in that operand precision (device tensors only)
     libsrbh_s2 = None       # None: stock 4x4 stride-2 convolutions; "f16": conv1..conv3 on libsrbh's 16-bit plane kernels (device tensors only)
+    libsrbh_wide = None     # None: act(conv4..conv8) as `libsrbh` says; "f16": conv + LeakyReLU as one function on 16-bit planes (device tensors only)
 
     def forward(self, x):
         act = lambda t: F.leaky_relu(t, 0.2)
@@ -279,20 +366,26 @@ class UNetDiscriminatorSN(nn.Module):
             s2 = _disc_conv4x4s2                                   # (4x4 stride 2 as 2x2 taps on space-to-depth planes)
         else:
             s2 = lambda conv, t: conv(t)                           # noqa: E731  (4x4 stride 2: stock convolutions)
+        c3a = lambda conv, t: act(c3(conv, t))                     # noqa: E731  (conv4..conv8 with their activation)
+        if self.libsrbh_wide is not None:
+            if self.libsrbh_wide != "f16":
+                raise ValueError(f"UNetDiscriminatorSN.libsrbh_wide: unknown mode {self.libsrbh_wide!r} (None or 'f16')")
+            if x.is_cuda:
+                c3a = lambda conv, t: _disc_conv3x3_act(conv, t, lambda c, u: act(c3(c, u)))      # noqa: E731  
         x0 = act(c3(self.conv0, x))
         x1 = act(s2(self.conv1, x0))
         x2 = act(s2(self.conv2, x1))
         x3 = act(s2(self.conv3, x2))
-        x4 = act(c3(self.conv4, up(x3)))
+        x4 = c3a(self.conv4, up(x3))
         if self.skip_connection:
             x4 = x4 + x2
-        x5 = act(c3(self.conv5, up(x4)))
+        x5 = c3a(self.conv5, up(x4))
         if self.skip_connection:
             x5 = x5 + x1
-        x6 = act(c3(self.conv6, up(x5)))
+        x6 = c3a(self.conv6, up(x5))
         if self.skip_connection:
             x6 = x6 + x0
-        return c3(self.conv9, act(c3(self.conv8, act(c3(self.conv7, x6)))))
+        return c3(self.conv9, c3a(self.conv8, c3a(self.conv7, x6)))
 
 
 def filter2D(img, kernel):
