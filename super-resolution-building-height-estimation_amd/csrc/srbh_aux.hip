@@ -1,5 +1,5 @@
 // srbh_aux.hip -- error plumbing, layout converters, weight packing and conv_first for libsrbh.
-#include "srbh_internal.h"
+#include "srbh_act16.h"
 
 namespace srbh {
 
@@ -116,25 +116,12 @@ __global__ void pack_w_kernel(const float* __restrict__ w, _Float16* __restrict_
     long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;  // one per packed half
     long total = (long)nchunk * 18 * nmb * 512;
     if (idx >= total) return;
-    int j = idx & 7;
-    int lane = (idx >> 3) & 63;
-    long f = idx >> 9;
-    int mb = f % nmb;
-    f /= nmb;
-    int ks = f & 1;
-    f >>= 1;
-    int tap = f % 9;
-    int chunk = f / 9;
-    int oc = mb * 32 + (lane & 31);
-    int ic = chunk * 32 + ks * 16 + (lane >> 5) * 8 + j;
-    float v = (oc < cout && ic < cin) ? w[((long)oc * cin + ic) * 9 + tap] : 0.f;
+    const WpackElem e = wpack_decode(idx, nmb, 9);
+    float v = (e.oc < cout && e.ic < cin) ? w[((long)e.oc * cin + e.ic) * 9 + e.tap] : 0.f;
     if constexpr (BF == 2) {     // the lo' part of the split-fp16 tail (srbh_ptail_split.hip): what fp16 leaves of v, scaled by 2^11
         out[idx] = (_Float16)((v - (float)(_Float16)v) * 2048.f);
-    } else if constexpr (BF) {   // bf16 (RNE) bits in the 16-bit slot
-        const unsigned u = __builtin_bit_cast(unsigned, v);
-        ((unsigned short*)out)[idx] = (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-    } else {
-        out[idx] = (_Float16)v;
+    } else {                     // fp16, or bf16 (RNE) bits in the 16-bit slot
+        ((unsigned short*)out)[idx] = to16(v, BF);
     }
 }
 
@@ -351,22 +338,10 @@ __global__ __launch_bounds__(256) void pack_w_many_kernel(const srbh_pack3x3_des
     if (d.bias_dst && idx < d.cout) d.bias_dst[idx] = d.bias_src[idx];
     const long total = (long)nchunk * 18 * nmb * 512;
     if (idx >= total) return;
-    const int j = idx & 7, lane = (idx >> 3) & 63;
-    long f = idx >> 9;
-    const int mb = f % nmb; f /= nmb;
-    const int ks = f & 1; f >>= 1;
-    const int tap = f % 9;
-    const int chunk = (int)(f / 9);
-    const int oc = mb * 32 + (lane & 31), ic = chunk * 32 + ks * 16 + (lane >> 5) * 8 + j;
-    const float v = (oc < d.cout && ic < d.cin) ? d.w[((long)oc * d.cin + ic) * 9 + tap] : 0.f;
-    if (d.bf16 == 2) {
-        ((_Float16*)d.packed)[idx] = (_Float16)((v - (float)(_Float16)v) * 2048.f);
-    } else if (d.bf16) {
-        const unsigned u = __builtin_bit_cast(unsigned, v);
-        ((unsigned short*)d.packed)[idx] = (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-    } else {
-        ((_Float16*)d.packed)[idx] = (_Float16)v;
-    }
+    const WpackElem e = wpack_decode(idx, nmb, 9);
+    const float v = (e.oc < d.cout && e.ic < d.cin) ? d.w[((long)e.oc * d.cin + e.ic) * 9 + e.tap] : 0.f;
+    if (d.bf16 == 2) ((_Float16*)d.packed)[idx] = (_Float16)((v - (float)(_Float16)v) * 2048.f);
+    else ((unsigned short*)d.packed)[idx] = to16(v, d.bf16);
 }
 
 extern "C" int srbh_pack_conv3x3_many(const srbh_pack3x3_desc* table_dev, int n, long max_elems, void* stream) {

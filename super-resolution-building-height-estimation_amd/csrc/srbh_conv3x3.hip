@@ -19,25 +19,10 @@
 // LDS bank conflicts: pixel records are 64 B, so the 16-B k-slot inside a record is XOR-swizzled with
 // (pixel_col>>2)&3; the swizzle is applied on the *source* address of the LDS-DMA (LDS-DMA writes are
 // lane-linear) and on the ds_read_b128 address -- same involution on both sides.
-#include "srbh_internal.h"
+#include "srbh_wconv_host.h"
 
-#include "srbh_conv3x3_kernel.h"
-
-namespace {
 using namespace srbh;
 using namespace srbh_k;
-
-template <int CB, int UPS, int BF = 0>
-int launch(const KParams& p, hipStream_t stream) {
-    constexpr int LDS_B = lds_bytes<CB, UPS>();
-    SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)conv3x3_f16_kernel<CB, UPS, 0, BF>,
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B)));
-    hipLaunchKernelGGL((conv3x3_f16_kernel<CB, UPS, 0, BF>), dim3(p.nblocks), dim3(256), LDS_B, stream, p);
-    SRBH_HIP(hipGetLastError());
-    return SRBH_OK;
-}
-
-}  // namespace
 
 static int conv3x3_impl(const srbh_conv3x3_args* a, const int bf16, const void* mask16, const int mask_chunks_total, const int mask_chunk0,
                         void* stream_) {
@@ -70,20 +55,8 @@ static int conv3x3_impl(const srbh_conv3x3_args* a, const int bf16, const void* 
     SRBH_REQUIRE(!ext || !a->upsample2x, "srbh_conv3x3_x16: the gradient forms have no nearest-x2 read");
     SRBH_REQUIRE(!mask16 || (mask_chunk0 >= 0 && mask_chunk0 + a->cout / 32 <= mask_chunks_total), "srbh_conv3x3_x16: mask chunk range outside its buffer");
 
-    const int inH = a->upsample2x ? a->H / 2 : a->H, inW = a->upsample2x ? a->W / 2 : a->W;
-    const Act16Geo gi = act16_geo(a->B, a->in_chunks_total, inH, inW);
-    KParams p;
-    p.in = (const char*)a->in + (long)a->in_chunk0 * gi.plane_b;
-    p.in_img_b = gi.img_b;
-    p.in_plane_b = gi.plane_b;
-    p.in_row_b = gi.row_b;
-    p.nchunk = a->in_chunks;
-    p.w = (const char*)a->w;
-    p.bias = a->bias;
-    p.H = a->H;
-    p.W = a->W;
-    p.tiles_x = (a->W + TILE_W - 1) / TILE_W;
-    p.tiles_per_img = p.tiles_x * ((a->H + TILE_H - 1) / TILE_H);
+    KParams p{};
+    conv_params_common(p, a, a->upsample2x ? a->H / 2 : a->H, a->upsample2x ? a->W / 2 : a->W);
     p.nblocks = p.tiles_per_img * a->B;
     p.lrelu = a->lrelu;
     p.res_scale = a->res_scale;
@@ -93,31 +66,13 @@ static int conv3x3_impl(const srbh_conv3x3_args* a, const int bf16, const void* 
     p.skip = a->skip;
     p.res1_update = a->res1_update;
     p.res2_update = a->res2_update;
-    p.out16 = nullptr;
-    p.out16_img_b = 0;
-    p.out16_plane_b = 0;
-    p.out16_row_b = 0;
-    if (a->out16) {
-        const Act16Geo go = act16_geo(a->B, a->out16_chunks_total, a->H, a->W);
-        p.out16 = (char*)a->out16 + (long)a->out16_chunk0 * go.plane_b;
-        p.out16_img_b = go.img_b;
-        p.out16_plane_b = go.plane_b;
-        p.out16_row_b = go.row_b;
-    }
-    p.out32 = a->out32;
-    p.out32_c = a->out32_c;
-    p.prof = nullptr;
-    p.mask16 = nullptr; p.mask_img_b = 0; p.mask_plane_b = 0; p.mask_row_b = 0;
-    if (mask16) {
-        const Act16Geo gm = act16_geo(a->B, mask_chunks_total, a->H, a->W);
-        p.mask16 = (const char*)mask16 + (long)mask_chunk0 * gm.plane_b;
-        p.mask_img_b = gm.img_b; p.mask_plane_b = gm.plane_b; p.mask_row_b = gm.row_b;
-    }
-    if (bf16 == 2) return a->cout == 64 ? launch<2, 0, 2>(p, stream) : launch<1, 0, 2>(p, stream);
-    if (bf16) return a->cout == 64 ? launch<2, 0, 1>(p, stream) : launch<1, 0, 1>(p, stream);
-
-    if (a->upsample2x) return a->cout == 64 ? launch<2, 1>(p, stream) : launch<1, 1>(p, stream);
-    return a->cout == 64 ? launch<2, 0>(p, stream) : launch<1, 0>(p, stream);
+    plane_arg(p.mask16, p.mask_img_b, p.mask_plane_b, p.mask_row_b, mask16, a->B, mask_chunks_total, mask_chunk0, a->H, a->W);
+    const int form = bf16 ? 1 + bf16 : a->upsample2x ? 1 : 0;      // (UPS, BF) = (0, 0), (1, 0), (0, 1), (0, 2)
+    return with_const<4>(form, [&](auto f) {
+        constexpr int UPS = decltype(f)::value == 1, BF = decltype(f)::value > 1 ? decltype(f)::value - 1 : 0;
+        return a->cout == 64 ? launch<conv3x3_f16_kernel<2, UPS, 0, BF>, true>(dim3(p.nblocks), lds_bytes<2, UPS>(), stream, p)
+                             : launch<conv3x3_f16_kernel<1, UPS, 0, BF>, true>(dim3(p.nblocks), lds_bytes<1, UPS>(), stream, p);
+    });
 }
 
 extern "C" int srbh_conv3x3_f16(const srbh_conv3x3_args* a, void* stream) { return conv3x3_impl(a, 0, nullptr, 0, 0, stream); }
@@ -136,82 +91,15 @@ extern "C" int srbh_conv3x3_x16(const srbh_conv3x3_args* a, int bf16, const void
 // The trunk's conv_tile (staging, swizzle, MFMA body, transposing epilogue) per (8 x 64 tile, 64-channel output slice); the slices of a tile
 // are neighbours in the XCD-remapped grid order, so the input tile they all stage comes out of L2 after the first.  Every wait in the body
 // is the full vmcnt(0) of conv_tile.
-namespace {
-template <int CB, int BF>
-int launch_wide(const WKParams& p, hipStream_t stream) {
-    constexpr int LDS_B = lds_bytes<CB, 0>();
-    SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)wconv3x3_kernel<CB, BF>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B)));
-    hipLaunchKernelGGL((wconv3x3_kernel<CB, BF>), dim3(p.nblocks), dim3(256), LDS_B, stream, p);
-    SRBH_HIP(hipGetLastError());
-    return SRBH_OK;
-}
-}  // namespace
-
-extern "C" int srbh_wconv3x3(const srbh_wconv3x3_args* a, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    SRBH_REQUIRE(a != nullptr, "srbh_wconv3x3: null args");
-    SRBH_REQUIRE(a->in && a->w, "srbh_wconv3x3: null input/weight pointer");
-    SRBH_REQUIRE(a->cout == 32 || (a->cout >= 64 && a->cout % 64 == 0), "srbh_wconv3x3: cout must be 32 or a multiple of 64 (got %d)", a->cout);
-    SRBH_REQUIRE(a->B > 0 && a->H > 0 && a->W > 0, "srbh_wconv3x3: bad geometry B=%d H=%d W=%d", a->B, a->H, a->W);
-    SRBH_REQUIRE(a->in_chunks >= 1 && a->in_chunk0 >= 0 && a->in_chunk0 + a->in_chunks <= a->in_chunks_total,
-                 "srbh_wconv3x3: input chunk range [%d,+%d) outside %d planes", a->in_chunk0, a->in_chunks, a->in_chunks_total);
-    SRBH_REQUIRE(a->out16 || a->out32, "srbh_wconv3x3: no output requested");
-    const int nmb = a->cout / 32;
-    SRBH_REQUIRE(!a->out16 || (a->out16_chunk0 >= 0 && a->out16_chunk0 + nmb <= a->out16_chunks_total), "srbh_wconv3x3: output chunk range outside its buffer");
-    SRBH_REQUIRE(!a->mask16 || (a->mask_chunk0 >= 0 && a->mask_chunk0 + nmb <= a->mask_chunks_total), "srbh_wconv3x3: mask chunk range outside its buffer");
-    SRBH_REQUIRE(!a->add16 || (a->add_chunk0 >= 0 && a->add_chunk0 + nmb <= a->add_chunks_total), "srbh_wconv3x3: addend chunk range outside its buffer");
-    SRBH_REQUIRE(!a->out32 || (a->out32_c >= 1 && a->out32_c <= a->cout), "srbh_wconv3x3: out32_c=%d invalid", a->out32_c);
-    const int cb = a->cout == 32 ? 1 : 2;
-    const long tiles = (long)((a->W + TILE_W - 1) / TILE_W) * ((a->H + TILE_H - 1) / TILE_H) * a->B;
-    SRBH_REQUIRE(tiles * (nmb / cb) < (1l << 30), "srbh_wconv3x3: too many workgroups");
-
-    const Act16Geo gi = act16_geo(a->B, a->in_chunks_total, a->H, a->W);
-    WKParams p;
-    p.in = (const char*)a->in + (long)a->in_chunk0 * gi.plane_b;
-    p.in_img_b = gi.img_b;
-    p.in_plane_b = gi.plane_b;
-    p.in_row_b = gi.row_b;
-    p.nchunk = a->in_chunks;
-    p.w = (const char*)a->w;
-    p.bias = a->bias;
-    p.H = a->H;
-    p.W = a->W;
-    p.tiles_x = (a->W + TILE_W - 1) / TILE_W;
-    p.tiles_per_img = p.tiles_x * ((a->H + TILE_H - 1) / TILE_H);
-    p.nslice = nmb / cb;
-    p.nblocks = p.tiles_per_img * a->B * p.nslice;
-    p.lrelu = 0;
-    p.res_scale = p.res2_scale = 0.f;
-    p.res1 = p.res2 = nullptr;
-    p.skip = nullptr;
-    p.res1_update = p.res2_update = 0;
-    p.out16 = nullptr; p.out16_img_b = 0; p.out16_plane_b = 0; p.out16_row_b = 0;
-    if (a->out16) {
-        const Act16Geo go = act16_geo(a->B, a->out16_chunks_total, a->H, a->W);
-        p.out16 = (char*)a->out16 + (long)a->out16_chunk0 * go.plane_b;
-        p.out16_img_b = go.img_b; p.out16_plane_b = go.plane_b; p.out16_row_b = go.row_b;
-    }
-    p.out32 = a->out32;
-    p.out32_c = a->out32_c;
-    p.prof = nullptr;
-    p.mask16 = nullptr; p.mask_img_b = 0; p.mask_plane_b = 0; p.mask_row_b = 0;
-    if (a->mask16) {
-        const Act16Geo gm = act16_geo(a->B, a->mask_chunks_total, a->H, a->W);
-        p.mask16 = (const char*)a->mask16 + (long)a->mask_chunk0 * gm.plane_b;
-        p.mask_img_b = gm.img_b; p.mask_plane_b = gm.plane_b; p.mask_row_b = gm.row_b;
-    }
-    p.add16 = nullptr; p.add_img_b = 0; p.add_plane_b = 0; p.add_row_b = 0;
-    if (a->add16) {
-        const Act16Geo ga = act16_geo(a->B, a->add_chunks_total, a->H, a->W);
-        p.add16 = (const char*)a->add16 + (long)a->add_chunk0 * ga.plane_b;
-        p.add_img_b = ga.img_b; p.add_plane_b = ga.plane_b; p.add_row_b = ga.row_b;
-    }
-    p.w_nmb = nmb;
-    p.w_chunk_b = 18 * 1024 * nmb;
-    p.relu = a->relu;
-    p.out32_c0 = 0;
-    if (a->bf16) return cb == 2 ? launch_wide<2, 1>(p, stream) : launch_wide<1, 1>(p, stream);
-    return cb == 2 ? launch_wide<2, 0>(p, stream) : launch_wide<1, 0>(p, stream);
+extern "C" int srbh_wconv3x3(const srbh_wconv3x3_args* a, void* stream) {
+    static constexpr WideForm form = {"srbh_wconv3x3", 3, 0, true, true, true, false};
+    if (const int rc = wide_validate(a, form)) return rc;
+    const WKParams p = wide_params(a, form);
+    return with_const<2>(a->bf16 != 0, [&](auto bf) {
+        constexpr int BF = decltype(bf)::value;
+        return a->cout == 32 ? launch<wconv3x3_kernel<1, BF>, true>(dim3(p.nblocks), lds_bytes<1, 0>(), (hipStream_t)stream, p)
+                             : launch<wconv3x3_kernel<2, BF>, true>(dim3(p.nblocks), lds_bytes<2, 0>(), (hipStream_t)stream, p);
+    });
 }
 
 int srbh::conv3x3_trunk_b16(const srbh_conv3x3_args* a, const int out_f16, void* stream) {

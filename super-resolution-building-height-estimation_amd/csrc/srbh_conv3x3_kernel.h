@@ -530,6 +530,8 @@ __global__ __launch_bounds__(256, 1) void conv3x3_f16_kernel(const KParams p) {
 }
 
 // The wide form's kernel: grid = tiles x nslice, consecutive ids of one XCD walk the slices of ONE tile (they share the staged input in L2).
+// (The three wide kernels repeat the remap / decode / slice shifts on purpose: through one shared inline body every one of their ten forms
+// compiled to other instructions, four of them to more registers and SGPR spills -- DESIGN.md 3.22, profiles/wide_host_path_isa.txt.)
 template <int CB, int BF>
 __global__ __launch_bounds__(256, 1) void wconv3x3_kernel(const WKParams p0) {
     extern __shared__ __attribute__((aligned(16))) char smem[];

@@ -10,39 +10,15 @@
 // depth-to-space, the entry point of the 2x2-tap form of the wide conv kernel (conv_tile<.., T2 = 1>, srbh_conv3x3_kernel.h) and the weight
 // gradient (a GEMM over pixels on v_mfma_f32_16x16x16_bf16, the construction of hwgrad_b16_kernel with two taps per axis and no halo).
 // Arithmetic contract: include/srbh.h, DESIGN.md 4.  No atomics anywhere: every result is bit-reproducible.
-#include "srbh_conv3x3_kernel.h"
+#include "srbh_act16.h"
+#include "srbh_wconv_host.h"
 
 namespace {
 using namespace srbh;
 using namespace srbh_k;
 
 typedef unsigned uint2w __attribute__((ext_vector_type(2)));
-typedef unsigned uint4w __attribute__((ext_vector_type(4)));
 typedef short short4w __attribute__((ext_vector_type(4)));
-
-struct PlaneGeo {
-    int row_b, plane_b;
-    long img_b;
-};
-inline PlaneGeo plane_geo(int B, int chunks, int H, int W) {
-    const Act16Geo g = act16_geo(B, chunks, H, W);
-    return PlaneGeo{g.row_b, g.plane_b, g.img_b};
-}
-inline unsigned blocks_of(long n) { return (unsigned)((n + 255) / 256); }
-inline bool fits(long units) { return units > 0 && units < (1l << 31) * 256; }
-
-// 8 fp32 -> 8 x 16 bit (RNE), fp16 or bf16
-template <int BF>
-__device__ __forceinline__ uint4w round8(const float (&v)[8]) {
-    if constexpr (BF) {
-        return uint4w{bf16x2_rne(v[0], v[1]), bf16x2_rne(v[2], v[3]), bf16x2_rne(v[4], v[5]), bf16x2_rne(v[6], v[7])};
-    } else {
-        half8 h;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) h[j] = (_Float16)v[j];
-        return __builtin_bit_cast(uint4w, h);
-    }
-}
 
 // ---- space-to-depth staging: fp32 NHWC (B, H, W, C) -> the planes of S.  One thread per (b, phase, u, v, octet): every record of the interior
 // is written, the pad-derived zeros (row 0 of the phases p = 0, row H/2 of p = 1, likewise the columns) included.
@@ -57,13 +33,9 @@ __global__ __launch_bounds__(256) void s2d_kernel(const float* __restrict__ x, c
     const int u = (int)(r % Hs); r /= Hs;
     const int ph = (int)(r & 3), b = (int)(r >> 2);
     const int y = 2 * u + (ph >> 1) - 1, xx = 2 * v + (ph & 1) - 1;
-    float val[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (y >= 0 && y < H && xx >= 0 && xx < W) {
-        const float* s = x + (((long)b * H + y) * W + xx) * C + o8 * 8;
-        const floatx4 a0 = *(const floatx4*)s, a1 = *(const floatx4*)(s + 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { val[j] = a0[j]; val[4 + j] = a1[j]; }
-    }
+    float val[8];
+    load8_or_zero(x, H, W, C, b, y, xx, o8, val);
+    // (rec_off written out: through the helper the sum is associated differently and this kernel takes 20 VGPRs for 18)
     char* o = planes + (long)b * g.img_b + (long)(ph * (C / 32) + (o8 >> 2)) * g.plane_b + (long)(u + 1) * g.row_b + (v + 1) * PIX_B + (o8 & 3) * 16;
     *(uint4w*)o = round8<BF>(val);
 }
@@ -79,16 +51,9 @@ __global__ __launch_bounds__(256) void framed_kernel(const float* __restrict__ x
     const int v = (int)(r % Wf); r /= Wf;
     const int u = (int)(r % Hf);
     const int b = (int)(r / Hf);
-    const int y = u - 1, xx = v - 1;
-    float val[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (y >= 0 && y < H && xx >= 0 && xx < W) {
-        const float* s = x + (((long)b * H + y) * W + xx) * C + o8 * 8;
-        const floatx4 a0 = *(const floatx4*)s, a1 = *(const floatx4*)(s + 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { val[j] = a0[j]; val[4 + j] = a1[j]; }
-    }
-    char* o = planes + (long)b * g.img_b + (long)(o8 >> 2) * g.plane_b + (long)(u + 1) * g.row_b + (v + 1) * PIX_B + (o8 & 3) * 16;
-    *(uint4w*)o = round8<BF>(val);
+    float val[8];
+    load8_or_zero(x, H, W, C, b, u - 1, v - 1, o8, val);
+    *(uint4w*)(planes + rec_off(g, b, o8 >> 2, u, v, o8 & 3)) = round8<BF>(val);
 }
 
 // ---- OIHW [O][C][4][4] fp32 -> the 2x2 pack [chunk][tap a*2+b][k-step][mb][lane][8] of a (cout, cin) weight; one thread per packed element.
@@ -96,29 +61,16 @@ __global__ __launch_bounds__(256) void framed_kernel(const float* __restrict__ x
 __device__ __forceinline__ void pack2x2_elem(const float* __restrict__ w, unsigned short* __restrict__ out, const int O, const int C, const int tf,
                                              const int bf, const long idx) {
     const int cout = tf ? 4 * C : O, cin = tf ? O : 4 * C;
-    const int nmb = cout / 32;
-    const int j = (int)(idx & 7), lane = (int)((idx >> 3) & 63);
-    long f = idx >> 9;
-    const int mb = (int)(f % nmb); f /= nmb;
-    const int ks = (int)(f & 1); f >>= 1;
-    const int tap = (int)(f & 3);
-    const int chunk = (int)(f >> 2);
-    const int oc = mb * 32 + (lane & 31), ic = chunk * 32 + ks * 16 + (lane >> 5) * 8 + j;
-    const int a = tap >> 1, b = tap & 1;
+    const WpackElem e = wpack_decode(idx, cout / 32, 4);
+    const int a = e.tap >> 1, b = e.tap & 1;
     float v = 0.f;
-    if (ic < cin) {
-        const int k = tf ? oc : ic, o = tf ? ic : oc;
+    if (e.ic < cin) {
+        const int k = tf ? e.oc : e.ic, o = tf ? e.ic : e.oc;
         const int ph = k / C, c = k - ph * C;
         const int ky = 2 * (tf ? 1 - a : a) + (ph >> 1), kx = 2 * (tf ? 1 - b : b) + (ph & 1);
         v = w[(((long)o * C + c) * 4 + ky) * 4 + kx];
     }
-    if (bf) {
-        const unsigned u = __builtin_bit_cast(unsigned, v);
-        out[idx] = (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-    } else {
-        const _Float16 h = (_Float16)v;
-        out[idx] = __builtin_bit_cast(unsigned short, h);
-    }
+    out[idx] = to16(v, bf);
 }
 __global__ __launch_bounds__(256) void pack2x2_kernel(const float* __restrict__ w, unsigned short* out, int O, int C, int tf, int bf, long total) {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
@@ -305,15 +257,6 @@ inline int wgrad_walkers(int O, int C, int B, int Ho, int Wo) {
     return (int)(n < ntiles ? n : ntiles);
 }
 
-template <int BF>
-int launch_wide2(const WKParams& p, hipStream_t stream) {
-    constexpr int LDS_B = lds_bytes<2, 0>();
-    SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)wconv2x2_kernel<2, BF>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B)));
-    hipLaunchKernelGGL((wconv2x2_kernel<2, BF>), dim3(p.nblocks), dim3(256), LDS_B, stream, p);
-    SRBH_HIP(hipGetLastError());
-    return SRBH_OK;
-}
-
 }  // namespace
 
 extern "C" int srbh_s2d_nhwc32_to_act16(const float* x, void* planes, int B, int C, int H, int W, int bf16, void* stream) {
@@ -381,51 +324,14 @@ extern "C" int srbh_d2s_nhwc32(const float* ds, float* dx, int B, int C, int H, 
     return SRBH_OK;
 }
 
-extern "C" int srbh_wconv2x2(const srbh_wconv3x3_args* a, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    SRBH_REQUIRE(a != nullptr, "srbh_wconv2x2: null args");
-    SRBH_REQUIRE(a->in && a->w && a->out32, "srbh_wconv2x2: null input / weight / out32 pointer");
-    SRBH_REQUIRE(a->cout >= 64 && a->cout % 64 == 0, "srbh_wconv2x2: cout must be a multiple of 64 (got %d)", a->cout);
-    SRBH_REQUIRE(a->B > 0 && a->H > 0 && a->W > 0, "srbh_wconv2x2: bad geometry B=%d H=%d W=%d", a->B, a->H, a->W);
-    SRBH_REQUIRE(a->in_chunks >= 1 && a->in_chunk0 >= 0 && a->in_chunk0 + a->in_chunks <= a->in_chunks_total,
-                 "srbh_wconv2x2: input chunk range [%d,+%d) outside %d planes", a->in_chunk0, a->in_chunks, a->in_chunks_total);
-    SRBH_REQUIRE(!a->bias && !a->relu && !a->mask16 && !a->add16 && !a->out16, "srbh_wconv2x2: no bias / relu / mask16 / add16 / out16 in this form");
-    SRBH_REQUIRE(a->out32_c == a->cout, "srbh_wconv2x2: out32_c=%d must equal cout=%d", a->out32_c, a->cout);
-    const int nmb = a->cout / 32;
-    const long tiles = (long)((a->W + TILE_W - 1) / TILE_W) * ((a->H + TILE_H - 1) / TILE_H) * a->B;
-    SRBH_REQUIRE(tiles * (nmb / 2) < (1l << 30), "srbh_wconv2x2: too many workgroups");
-
-    const Act16Geo gi = act16_geo(a->B, a->in_chunks_total, a->H + 1, a->W + 1);      // the input interior is (H+1) x (W+1)
-    WKParams p;
-    p.in = (const char*)a->in + (long)a->in_chunk0 * gi.plane_b;
-    p.in_img_b = gi.img_b;
-    p.in_plane_b = gi.plane_b;
-    p.in_row_b = gi.row_b;
-    p.nchunk = a->in_chunks;
-    p.w = (const char*)a->w;
-    p.bias = nullptr;
-    p.H = a->H;
-    p.W = a->W;
-    p.tiles_x = (a->W + TILE_W - 1) / TILE_W;
-    p.tiles_per_img = p.tiles_x * ((a->H + TILE_H - 1) / TILE_H);
-    p.nslice = nmb / 2;
-    p.nblocks = p.tiles_per_img * a->B * p.nslice;
-    p.lrelu = 0;
-    p.res_scale = p.res2_scale = 0.f;
-    p.res1 = p.res2 = nullptr;
-    p.skip = nullptr;
-    p.res1_update = p.res2_update = 0;
-    p.out16 = nullptr; p.out16_img_b = 0; p.out16_plane_b = 0; p.out16_row_b = 0;
-    p.out32 = a->out32;
-    p.out32_c = a->out32_c;
-    p.prof = nullptr;
-    p.mask16 = nullptr; p.mask_img_b = 0; p.mask_plane_b = 0; p.mask_row_b = 0;
-    p.add16 = nullptr; p.add_img_b = 0; p.add_plane_b = 0; p.add_row_b = 0;
-    p.w_nmb = nmb;
-    p.w_chunk_b = 8 * 1024 * nmb;
-    p.relu = 0;
-    p.out32_c0 = 0;
-    return a->bf16 ? launch_wide2<1>(p, stream) : launch_wide2<0>(p, stream);
+// the 2x2-tap VALID form of the wide conv: input interior (H+1) x (W+1), cout a multiple of 64, fp32 NHWC output of all channels only
+extern "C" int srbh_wconv2x2(const srbh_wconv3x3_args* a, void* stream) {
+    static constexpr WideForm form = {"srbh_wconv2x2", 2, 1, false, false, false, true};
+    if (const int rc = wide_validate(a, form)) return rc;
+    const WKParams p = wide_params(a, form);
+    return with_const<2>(a->bf16 != 0, [&](auto bf) {
+        return launch<wconv2x2_kernel<2, decltype(bf)::value>, true>(dim3(p.nblocks), lds_bytes<2, 0>(), (hipStream_t)stream, p);
+    });
 }
 
 extern "C" size_t srbh_wgrad4x4s2_ws_bytes(int O, int C, int B, int Ho, int Wo) {

@@ -8,24 +8,21 @@
 // 8 x 64 tiles blockIdx.x, + walkers, ...; each of its four waves owns 16 of the 64 output channels (72 accumulator registers), so the waves never
 // meet and one staged tile (32 channels of x with a halo, 64 of g', both channel-major: K of the MFMA is the pixel axis) serves 1152 MFMAs.
 // Arithmetic contract: include/srbh.h, DESIGN.md 4.  No atomics anywhere: every result is bit-reproducible.
-#include "srbh_conv3x3_kernel.h"
+#include "srbh_act16.h"
+#include "srbh_wconv_host.h"
 
 namespace {
 using namespace srbh;
 using namespace srbh_k;
 
 typedef unsigned uint2w __attribute__((ext_vector_type(2)));
-typedef unsigned uint4w __attribute__((ext_vector_type(4)));
 typedef _Float16 half8w __attribute__((ext_vector_type(8)));
-
-inline unsigned blocks_of(long n) { return (unsigned)((n + 255) / 256); }
-inline bool fits(long units) { return units > 0 && units < (1l << 31) * 256; }
 
 // ---- masked gradient staging: fp32 NHWC g and the saved fp32 NHWC forward output y -> chunk planes of rne(g * (y > 0 ? 1 : slope)), the product
 // in fp32 (torch's leaky_relu backward rule, srbh_lrelu_bwd_f32's).  One thread per (pixel, 8-channel octet): two 32-byte reads, one 16-byte write.
 template <int BF>
 __global__ __launch_bounds__(256) void lrelu_bwd_stage_kernel(const float* __restrict__ g, const float* __restrict__ y, char* planes, int B, int C, int H,
-                                                              int W, float slope, int row_b, int plane_b, long img_b) {
+                                                              int W, float slope, PlaneGeo geo) {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     const int oct = C / 8;
     if (idx >= (long)B * H * W * oct) return;
@@ -43,41 +40,19 @@ __global__ __launch_bounds__(256) void lrelu_bwd_stage_kernel(const float* __res
         v[j] = y0[j] > 0.f ? g0[j] : g0[j] * slope;
         v[4 + j] = y1[j] > 0.f ? g1[j] : g1[j] * slope;
     }
-    uint4w pk;
-    if constexpr (BF) {
-        pk = uint4w{bf16x2_rne(v[0], v[1]), bf16x2_rne(v[2], v[3]), bf16x2_rne(v[4], v[5]), bf16x2_rne(v[6], v[7])};
-    } else {
-        half8w h;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) h[j] = (_Float16)v[j];
-        pk = __builtin_bit_cast(uint4w, h);
-    }
-    *(uint4w*)(planes + (long)b * img_b + (long)(o8 >> 2) * plane_b + (long)(yy + 1) * row_b + (x + 1) * PIX_B + (o8 & 3) * 16) = pk;
+    *(uint4w*)(planes + rec_off(geo, b, o8 >> 2, yy, x, o8 & 3)) = round8<BF>(v);
 }
 
-// ---- both packs of one weight in one launch: blockIdx.y = 0 the fp16 WPACK16 of w (cout, cin), 1 the bf16 WPACK16 of Wt (cin, cout).  The index
-// arithmetic is pack_w_kernel's (srbh_aux.hip): [chunk][tap][k-step][mb][lane][8]; with both channel counts multiples of 32 the packs have one size.
+// ---- both packs of one weight in one launch: blockIdx.y = 0 the fp16 WPACK16 of w (cout, cin), 1 the bf16 WPACK16 of Wt (cin, cout).  The layout
+// is pack_w_kernel's (srbh_aux.hip; wpack_decode): [chunk][tap][k-step][mb][lane][8]; with both channel counts multiples of 32 the packs have one size.
 __global__ __launch_bounds__(256) void pack3x3_pair_kernel(const float* __restrict__ w, unsigned short* __restrict__ wf, unsigned short* __restrict__ wt,
                                                            int cout, int cin, long total) {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= total) return;
     const int tf = blockIdx.y;
-    const int nmb = (tf ? cin : cout) / 32;
-    const int j = (int)(idx & 7), lane = (int)((idx >> 3) & 63);
-    long f = idx >> 9;
-    const int mb = (int)(f % nmb); f /= nmb;
-    const int ks = (int)(f & 1); f >>= 1;
-    const int tap = (int)(f % 9);
-    const int chunk = (int)(f / 9);
-    const int oc = mb * 32 + (lane & 31), ic = chunk * 32 + ks * 16 + (lane >> 5) * 8 + j;
-    if (tf) {
-        const float v = w[((long)ic * cin + oc) * 9 + (8 - tap)];        // Wt[oc][ic][a][b] = w[ic][oc][2-a][2-b]
-        const unsigned u = __builtin_bit_cast(unsigned, v);
-        wt[idx] = (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-    } else {
-        const _Float16 h = (_Float16)w[((long)oc * cin + ic) * 9 + tap];
-        wf[idx] = __builtin_bit_cast(unsigned short, h);
-    }
+    const WpackElem e = wpack_decode(idx, (tf ? cin : cout) / 32, 9);
+    if (tf) wt[idx] = to16(w[((long)e.ic * cin + e.oc) * 9 + (8 - e.tap)], 1);        // Wt[oc][ic][a][b] = w[ic][oc][2-a][2-b]
+    else wf[idx] = to16(w[((long)e.oc * cin + e.ic) * 9 + e.tap], 0);
 }
 
 // ---- weight gradient --------------------------------------------------------------------------------------------------------------------
@@ -268,71 +243,18 @@ inline bool wgrad3_shape_ok(int cout, int cin, int B, int H, int W) {
     return B > 0 && H > 0 && W > 0 && cin > 0 && (cin & 31) == 0 && (cout == 32 || (cout >= 64 && cout % 64 == 0)) && cout / 64 <= 65535 && cin / 32 <= 65535;
 }
 
-template <int CB, int BF>
-int launch_wide_lrelu(const WKParams& p, hipStream_t stream) {
-    constexpr int LDS_B = lds_bytes<CB, 0>();
-    SRBH_ONCE_PER_DEVICE(SRBH_HIP(hipFuncSetAttribute((const void*)wconv3x3_lrelu_kernel<CB, BF>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B)));
-    hipLaunchKernelGGL((wconv3x3_lrelu_kernel<CB, BF>), dim3(p.nblocks), dim3(256), LDS_B, stream, p);
-    SRBH_HIP(hipGetLastError());
-    return SRBH_OK;
-}
-
 }  // namespace
 
-extern "C" int srbh_wconv3x3_lrelu(const srbh_wconv3x3_args* a, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    SRBH_REQUIRE(a != nullptr, "srbh_wconv3x3_lrelu: null args");
-    SRBH_REQUIRE(a->in && a->w, "srbh_wconv3x3_lrelu: null input / weight pointer");
-    SRBH_REQUIRE(a->cout == 32 || (a->cout >= 64 && a->cout % 64 == 0), "srbh_wconv3x3_lrelu: cout must be 32 or a multiple of 64 (got %d)", a->cout);
-    SRBH_REQUIRE(a->B > 0 && a->H > 0 && a->W > 0, "srbh_wconv3x3_lrelu: bad geometry B=%d H=%d W=%d", a->B, a->H, a->W);
-    SRBH_REQUIRE(a->in_chunks >= 1 && a->in_chunk0 >= 0 && a->in_chunk0 + a->in_chunks <= a->in_chunks_total,
-                 "srbh_wconv3x3_lrelu: input chunk range [%d,+%d) outside %d planes", a->in_chunk0, a->in_chunks, a->in_chunks_total);
-    SRBH_REQUIRE(!a->bias && !a->relu && !a->mask16 && !a->add16, "srbh_wconv3x3_lrelu: no bias / relu / mask16 / add16 in this form");
-    SRBH_REQUIRE(a->out16 || a->out32, "srbh_wconv3x3_lrelu: no output requested");
-    const int nmb = a->cout / 32;
-    SRBH_REQUIRE(!a->out16 || (a->out16_chunk0 >= 0 && a->out16_chunk0 + nmb <= a->out16_chunks_total), "srbh_wconv3x3_lrelu: output chunk range outside its buffer");
-    SRBH_REQUIRE(!a->out32 || (a->out32_c >= 1 && a->out32_c <= a->cout), "srbh_wconv3x3_lrelu: out32_c=%d invalid", a->out32_c);
-    const int cb = a->cout == 32 ? 1 : 2;
-    const long tiles = (long)((a->W + TILE_W - 1) / TILE_W) * ((a->H + TILE_H - 1) / TILE_H) * a->B;
-    SRBH_REQUIRE(tiles * (nmb / cb) < (1l << 30), "srbh_wconv3x3_lrelu: too many workgroups");
-
-    const Act16Geo gi = act16_geo(a->B, a->in_chunks_total, a->H, a->W);
-    WKParams p;
-    p.in = (const char*)a->in + (long)a->in_chunk0 * gi.plane_b;
-    p.in_img_b = gi.img_b;
-    p.in_plane_b = gi.plane_b;
-    p.in_row_b = gi.row_b;
-    p.nchunk = a->in_chunks;
-    p.w = (const char*)a->w;
-    p.bias = nullptr;
-    p.H = a->H;
-    p.W = a->W;
-    p.tiles_x = (a->W + TILE_W - 1) / TILE_W;
-    p.tiles_per_img = p.tiles_x * ((a->H + TILE_H - 1) / TILE_H);
-    p.nslice = nmb / cb;
-    p.nblocks = p.tiles_per_img * a->B * p.nslice;
-    p.lrelu = 0;
-    p.res_scale = p.res2_scale = 0.f;
-    p.res1 = p.res2 = nullptr;
-    p.skip = nullptr;
-    p.res1_update = p.res2_update = 0;
-    p.out16 = nullptr; p.out16_img_b = 0; p.out16_plane_b = 0; p.out16_row_b = 0;
-    if (a->out16) {
-        const Act16Geo go = act16_geo(a->B, a->out16_chunks_total, a->H, a->W);
-        p.out16 = (char*)a->out16 + (long)a->out16_chunk0 * go.plane_b;
-        p.out16_img_b = go.img_b; p.out16_plane_b = go.plane_b; p.out16_row_b = go.row_b;
-    }
-    p.out32 = a->out32;
-    p.out32_c = a->out32_c;
-    p.prof = nullptr;
-    p.mask16 = nullptr; p.mask_img_b = 0; p.mask_plane_b = 0; p.mask_row_b = 0;
-    p.add16 = nullptr; p.add_img_b = 0; p.add_plane_b = 0; p.add_row_b = 0;
-    p.w_nmb = nmb;
-    p.w_chunk_b = 18 * 1024 * nmb;
-    p.relu = 0;
-    p.out32_c0 = 0;
-    if (a->bf16) return cb == 2 ? launch_wide_lrelu<2, 1>(p, stream) : launch_wide_lrelu<1, 1>(p, stream);
-    return cb == 2 ? launch_wide_lrelu<2, 0>(p, stream) : launch_wide_lrelu<1, 0>(p, stream);
+// the wide 3x3 conv with the forward LeakyReLU(0.2) in its epilogue: no bias / relu / mask16 / add16
+extern "C" int srbh_wconv3x3_lrelu(const srbh_wconv3x3_args* a, void* stream) {
+    static constexpr WideForm form = {"srbh_wconv3x3_lrelu", 3, 0, true, false, true, false};
+    if (const int rc = wide_validate(a, form)) return rc;
+    const WKParams p = wide_params(a, form);
+    return with_const<2>(a->bf16 != 0, [&](auto bf) {
+        constexpr int BF = decltype(bf)::value;
+        return a->cout == 32 ? launch<wconv3x3_lrelu_kernel<1, BF>, true>(dim3(p.nblocks), lds_bytes<1, 0>(), (hipStream_t)stream, p)
+                             : launch<wconv3x3_lrelu_kernel<2, BF>, true>(dim3(p.nblocks), lds_bytes<2, 0>(), (hipStream_t)stream, p);
+    });
 }
 
 extern "C" int srbh_nhwc32_to_act16_lrelu_bwd(const float* g, const float* y, void* planes, int B, int C, int H, int W, float slope, int bf16, void* stream) {
@@ -341,11 +263,9 @@ extern "C" int srbh_nhwc32_to_act16_lrelu_bwd(const float* g, const float* y, vo
     SRBH_REQUIRE(H > 0 && W > 0, "srbh_nhwc32_to_act16_lrelu_bwd: bad geometry %dx%d", H, W);
     const long total = (long)B * H * W * (C / 8);
     SRBH_REQUIRE(fits(total), "srbh_nhwc32_to_act16_lrelu_bwd: too large");
-    const Act16Geo ge = act16_geo(B, C / 32, H, W);
-    if (bf16) hipLaunchKernelGGL(lrelu_bwd_stage_kernel<1>, dim3(blocks_of(total)), dim3(256), 0, (hipStream_t)stream, g, y, (char*)planes, B, C, H, W, slope,
-                                 ge.row_b, ge.plane_b, ge.img_b);
-    else hipLaunchKernelGGL(lrelu_bwd_stage_kernel<0>, dim3(blocks_of(total)), dim3(256), 0, (hipStream_t)stream, g, y, (char*)planes, B, C, H, W, slope,
-                            ge.row_b, ge.plane_b, ge.img_b);
+    const PlaneGeo ge = plane_geo(B, C / 32, H, W);
+    if (bf16) hipLaunchKernelGGL(lrelu_bwd_stage_kernel<1>, dim3(blocks_of(total)), dim3(256), 0, (hipStream_t)stream, g, y, (char*)planes, B, C, H, W, slope, ge);
+    else hipLaunchKernelGGL(lrelu_bwd_stage_kernel<0>, dim3(blocks_of(total)), dim3(256), 0, (hipStream_t)stream, g, y, (char*)planes, B, C, H, W, slope, ge);
     SRBH_HIP(hipGetLastError());
     return SRBH_OK;
 }

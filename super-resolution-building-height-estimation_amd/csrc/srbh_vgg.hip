@@ -4,7 +4,7 @@
 //
 // Every kernel owns one 16-byte octet (8 channels) of a pixel record per thread and touches the INTERIOR of its ACT16 planes only: the
 // zero borders the convs rely on are written once by whoever allocates the buffers.  No atomics; the distance is bit-reproducible.
-#include "srbh_internal.h"
+#include "srbh_act16.h"
 
 namespace {
 using namespace srbh;
@@ -12,17 +12,6 @@ using namespace srbh;
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef unsigned uint4e __attribute__((ext_vector_type(4)));
 
-struct PlaneGeo {
-    int row_b, plane_b;
-    long img_b;
-};
-inline PlaneGeo plane_geo(int B, int chunks, int H, int W) {
-    const Act16Geo g = act16_geo(B, chunks, H, W);
-    return PlaneGeo{g.row_b, g.plane_b, g.img_b};
-}
-__device__ __forceinline__ long rec_off(const PlaneGeo& g, int b, int ch, int y, int x, int oct) {
-    return (long)b * g.img_b + (long)ch * g.plane_b + (long)(y + 1) * g.row_b + (x + 1) * PIX_B + oct * 16;
-}
 // unit index -> (b, chunk, y, x, octet); octet fastest, so that 4 neighbouring threads cover one 64-byte record
 __device__ __forceinline__ void unit_of(long idx, int chunks, int H, int W, int& b, int& ch, int& y, int& x, int& oct) {
     oct = (int)(idx & 3);
@@ -141,8 +130,7 @@ __global__ __launch_bounds__(256) void vgg_relu_pool_bwd_kernel(const char* __re
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] += (j & 1) ? bf16_hi(au[j >> 1]) : bf16_lo(au[j >> 1]);
     }
-    const uint4e pk = {bf16x2_rne(v[0], v[1]), bf16x2_rne(v[2], v[3]), bf16x2_rne(v[4], v[5]), bf16x2_rne(v[6], v[7])};
-    *(uint4e*)(out + rec_off(gf, b, ch, y, x, oct)) = pk;
+    *(uint4e*)(out + rec_off(gf, b, ch, y, x, oct)) = round8<1>(v);
 }
 
 // sum of v over the 256 threads in a fixed order; valid in thread 0
@@ -186,10 +174,7 @@ __global__ __launch_bounds__(256) void vgg_dist_kernel(const char* __restrict__ 
                     gv[j] = d > 0 ? gscale : (d < 0 ? -gscale : 0.f);
                 }
             }
-            if (grad) {
-                const uint4e pk = {bf16x2_rne(gv[0], gv[1]), bf16x2_rne(gv[2], gv[3]), bf16x2_rne(gv[4], gv[5]), bf16x2_rne(gv[6], gv[7])};
-                *(uint4e*)(grad + off) = pk;
-            }
+            if (grad) *(uint4e*)(grad + off) = round8<1>(gv);
         }
     }
     const double t = block_sum(s, red);
@@ -222,9 +207,6 @@ __global__ __launch_bounds__(256) void vgg_dx_kernel(const float* __restrict__ g
     if (sc.range) v = v / 2.0f;
     dx[idx] = v * go[0];
 }
-
-inline unsigned blocks_of(long n) { return (unsigned)((n + 255) / 256); }
-inline bool fits(long units) { return units > 0 && units < (1l << 31) * 256; }
 
 }  // namespace
 

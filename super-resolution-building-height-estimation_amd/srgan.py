@@ -116,18 +116,46 @@ class _DiscConvFn(torch.autograd.Function):
         return dx, dw, db, None
 
 
-def _disc_conv3x3(conv, x, h16):
-    """conv(x) of a 3x3 stride-1 discriminator conv on libsrbh.  torch's spectral_norm is a forward PRE-hook that sets conv.weight =
-    weight_orig / sigma (one power iteration in training): it is the only hook this path knows how to honour, so it is called by hand and a
-    module carrying ANY other hook (forward hooks, foreign pre-hooks, hooks with kwargs) takes the stock `conv(x)` with the full hook protocol."""
+def _sn_hooks_by_hand(conv, x):
+    """The hook protocol of the discriminator convs on libsrbh.  torch's spectral_norm is a forward PRE-hook that sets conv.weight =
+    weight_orig / sigma (one power iteration in training): it is the only hook these paths know how to honour.  A module that carries nothing
+    but such pre-hooks gets them called by hand -> True, and the caller reads conv.weight; a module carrying ANY other hook (forward hooks,
+    foreign pre-hooks, hooks with kwargs) is left alone -> False, and the caller takes the stock path with the full hook protocol."""
     from torch.nn.utils.spectral_norm import SpectralNorm
     pre = list(conv._forward_pre_hooks.values())
     if (any(not isinstance(h, SpectralNorm) for h in pre) or conv._forward_hooks or conv._backward_hooks or conv._backward_pre_hooks
             or getattr(conv, "_forward_pre_hooks_with_kwargs", None) or getattr(conv, "_forward_hooks_with_kwargs", None)):
-        return conv(x)
+        return False
     for hook in pre:
         hook(conv, (x,))
+    return True
+
+
+def _disc_conv3x3(conv, x, h16):
+    """conv(x) of a 3x3 stride-1 discriminator conv on libsrbh, under the hook protocol of _sn_hooks_by_hand"""
+    if not _sn_hooks_by_hand(conv, x):
+        return conv(x)
     return _DiscConvFn.apply(x, conv.weight, conv.bias, h16)
+
+
+def _wconv(inp, in_chunks, w, bias, cout, B, H, W, bf16=0, relu=0, mask=None, add=None, out16=None, out32=None, out32_c=0,
+           entry="srbh_wconv3x3", label="wconv3x3(vgg)"):
+    """one call of a wide conv entry point (include/srbh.h: srbh_wconv3x3, srbh_wconv2x2, srbh_wconv3x3_lrelu) on whole plane buffers"""
+    import ctypes as C
+    from . import _lib
+    a = _lib.WConvArgs()
+    a.in_, a.in_chunks_total, a.in_chunk0, a.in_chunks = inp.data_ptr(), in_chunks, 0, in_chunks
+    a.w, a.bias, a.cout = w.data_ptr(), (None if bias is None else bias.data_ptr()), cout
+    a.B, a.H, a.W, a.bf16, a.relu = B, H, W, bf16, relu
+    if mask is not None:
+        a.mask16, a.mask_chunks_total, a.mask_chunk0 = mask.data_ptr(), cout // 32, 0
+    if add is not None:
+        a.add16, a.add_chunks_total, a.add_chunk0 = add.data_ptr(), cout // 32, 0
+    if out16 is not None:
+        a.out16, a.out16_chunks_total, a.out16_chunk0 = out16.data_ptr(), cout // 32, 0
+    if out32 is not None:
+        a.out32, a.out32_c = out32.data_ptr(), out32_c
+    _lib.check(getattr(_lib.lib(), entry)(C.byref(a), _lib.stream_ptr()), label)
 
 
 # ---- the three 4x4 stride-2 convs on libsrbh (UNetDiscriminatorSN.libsrbh_s2 = "f16") -------------------------------------------------------
@@ -139,7 +167,6 @@ def _disc_conv3x3(conv, x, h16):
 class _DiscConvS2Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight):
-        import ctypes as C
         from . import _lib
         from . import hrfuse as H
         L, sp = _lib.lib(), _lib.stream_ptr
@@ -156,18 +183,13 @@ class _DiscConvS2Fn(torch.autograd.Function):
             w2, wt = torch.empty(nb, dtype=torch.uint8, device=dev), torch.empty(nb, dtype=torch.uint8, device=dev)
             _lib.check(L.srbh_pack_conv4x4s2_pair(w.data_ptr(), O, Cc, w2.data_ptr(), wt.data_ptr(), sp()), "pack_conv4x4s2_pair(disc)")
             out = H.empty_nhwc(B, O, Ho, Wo, dev)
-            a = _lib.WConvArgs()
-            a.in_, a.in_chunks_total, a.in_chunk0, a.in_chunks = S.data_ptr(), Cc // 8, 0, Cc // 8
-            a.w, a.cout, a.B, a.H, a.W = w2.data_ptr(), O, B, Ho, Wo
-            a.out32, a.out32_c = out.data_ptr(), O
-            _lib.check(L.srbh_wconv2x2(C.byref(a), sp()), "wconv2x2(disc fwd)")
+            _wconv(S, Cc // 8, w2, None, O, B, Ho, Wo, out32=out, out32_c=O, entry="srbh_wconv2x2", label="wconv2x2(disc fwd)")
         ctx.save_for_backward(S, wt)
         ctx.geo = (B, Cc, O, Hh, Ww)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        import ctypes as C
         from . import _lib
         from . import hrfuse as H
         L, sp = _lib.lib(), _lib.stream_ptr
@@ -184,11 +206,8 @@ class _DiscConvS2Fn(torch.autograd.Function):
             _lib.check(L.srbh_nhwc32_to_act16_framed(gn.data_ptr(), G.data_ptr(), B, O, Ho, Wo, 1, sp()), "nhwc32_to_act16_framed(disc)")
             if ctx.needs_input_grad[0]:
                 ds = torch.empty((B, Ho + 1, Wo + 1, 4 * Cc), dtype=torch.float32, device=dev)
-                a = _lib.WConvArgs()
-                a.in_, a.in_chunks_total, a.in_chunk0, a.in_chunks = G.data_ptr(), O // 32, 0, O // 32
-                a.w, a.cout, a.B, a.H, a.W, a.bf16 = wt.data_ptr(), 4 * Cc, B, Ho + 1, Wo + 1, 1
-                a.out32, a.out32_c = ds.data_ptr(), 4 * Cc
-                _lib.check(L.srbh_wconv2x2(C.byref(a), sp()), "wconv2x2(disc dgrad)")
+                _wconv(G, O // 32, wt, None, 4 * Cc, B, Ho + 1, Wo + 1, bf16=1, out32=ds, out32_c=4 * Cc, entry="srbh_wconv2x2",
+                       label="wconv2x2(disc dgrad)")
                 dx = H.empty_nhwc(B, Cc, Hh, Ww, dev)
                 _lib.check(L.srbh_d2s_nhwc32(ds.data_ptr(), dx.data_ptr(), B, Cc, Hh, Ww, sp()), "d2s_nhwc32(disc)")
             if ctx.needs_input_grad[1]:
@@ -199,22 +218,17 @@ class _DiscConvS2Fn(torch.autograd.Function):
 
 
 def _disc_conv4x4s2(conv, x):
-    """conv(x) of a 4x4 / stride 2 / pad 1 discriminator conv on libsrbh (_DiscConvS2Fn), under the hook protocol of _disc_conv3x3: spectral
+    """conv(x) of a 4x4 / stride 2 / pad 1 discriminator conv on libsrbh (_DiscConvS2Fn), under the hook protocol of _sn_hooks_by_hand: spectral
     norm's pre-hook is called by hand, a module with any other hook takes stock `conv(x)`.  So does every conv or input outside what the kernels
     take (bias, other geometry, in_channels % 64, out_channels % 64, odd H or W, CPU tensors).  The kernels themselves take in_channels % 32
     (include/srbh.h); the module asks for 64, the narrowest conv1 of a discriminator this mode is meant for (num_feat 64: 64 / 128 / 256), so that
     the 8-feature net of fixture g14 -- whose conv3 is 32 -> 64 -- keeps stock fp32 convolutions and its 2e-5 agreement with the reference."""
-    from torch.nn.utils.spectral_norm import SpectralNorm
     ok = (isinstance(conv, nn.Conv2d) and conv.kernel_size == (4, 4) and conv.stride == (2, 2) and conv.padding == (1, 1)
           and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None and conv.padding_mode == "zeros"
           and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0
           and x.dim() == 4 and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and x.is_cuda)
-    pre = list(conv._forward_pre_hooks.values())
-    if (not ok or any(not isinstance(h, SpectralNorm) for h in pre) or conv._forward_hooks or conv._backward_hooks or conv._backward_pre_hooks
-            or getattr(conv, "_forward_pre_hooks_with_kwargs", None) or getattr(conv, "_forward_hooks_with_kwargs", None)):
+    if not ok or not _sn_hooks_by_hand(conv, x):
         return conv(x)
-    for hook in pre:
-        hook(conv, (x,))
     return _DiscConvS2Fn.apply(x, conv.weight)
 
 
@@ -228,7 +242,6 @@ def _disc_conv4x4s2(conv, x):
 class _DiscConvWideFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight):
-        import ctypes as C
         from . import _lib
         from . import hrfuse as H
         L, sp = _lib.lib(), _lib.stream_ptr
@@ -244,18 +257,13 @@ class _DiscConvWideFn(torch.autograd.Function):
             wf, wt = torch.empty(nb, dtype=torch.uint8, device=dev), torch.empty(nb, dtype=torch.uint8, device=dev)
             _lib.check(L.srbh_pack_conv3x3_pair(w.data_ptr(), O, Cc, wf.data_ptr(), wt.data_ptr(), sp()), "pack_conv3x3_pair(disc wide)")
             y = H.empty_nhwc(B, O, Hh, Ww, dev)
-            a = _lib.WConvArgs()
-            a.in_, a.in_chunks_total, a.in_chunk0, a.in_chunks = X.data_ptr(), Cc // 32, 0, Cc // 32
-            a.w, a.cout, a.B, a.H, a.W = wf.data_ptr(), O, B, Hh, Ww
-            a.out32, a.out32_c = y.data_ptr(), O
-            _lib.check(L.srbh_wconv3x3_lrelu(C.byref(a), sp()), "wconv3x3_lrelu(disc fwd)")
+            _wconv(X, Cc // 32, wf, None, O, B, Hh, Ww, out32=y, out32_c=O, entry="srbh_wconv3x3_lrelu", label="wconv3x3_lrelu(disc fwd)")
         ctx.save_for_backward(X, y, wt)
         ctx.geo = (B, Cc, O, Hh, Ww)
         return y
 
     @staticmethod
     def backward(ctx, g):
-        import ctypes as C
         from . import _lib
         from . import hrfuse as H
         L, sp = _lib.lib(), _lib.stream_ptr
@@ -271,11 +279,7 @@ class _DiscConvWideFn(torch.autograd.Function):
             _lib.check(L.srbh_nhwc32_to_act16_lrelu_bwd(gn.data_ptr(), y.data_ptr(), G.data_ptr(), B, O, Hh, Ww, 0.2, 1, sp()), "nhwc32_to_act16_lrelu_bwd(disc)")
             if ctx.needs_input_grad[0]:
                 dx = H.empty_nhwc(B, Cc, Hh, Ww, dev)
-                a = _lib.WConvArgs()
-                a.in_, a.in_chunks_total, a.in_chunk0, a.in_chunks = G.data_ptr(), O // 32, 0, O // 32
-                a.w, a.cout, a.B, a.H, a.W, a.bf16 = wt.data_ptr(), Cc, B, Hh, Ww, 1
-                a.out32, a.out32_c = dx.data_ptr(), Cc
-                _lib.check(L.srbh_wconv3x3(C.byref(a), sp()), "wconv3x3(disc dgrad)")
+                _wconv(G, O // 32, wt, None, Cc, B, Hh, Ww, bf16=1, out32=dx, out32_c=Cc, label="wconv3x3(disc dgrad)")
             if ctx.needs_input_grad[1]:
                 dw = torch.empty((O, Cc, 3, 3), dtype=torch.float32, device=dev)
                 ws = torch.empty(L.srbh_wgrad3x3_ws_bytes(O, Cc, B, Hh, Ww) // 4, dtype=torch.float32, device=dev)
@@ -286,20 +290,15 @@ class _DiscConvWideFn(torch.autograd.Function):
 
 def _disc_conv3x3_act(conv, x, stock):
     """leaky_relu(conv(x), 0.2) of a wide 3x3 stride-1 discriminator conv on libsrbh (_DiscConvWideFn), under the hook protocol of
-    _disc_conv4x4s2: spectral norm's pre-hook is called by hand, a module with any other hook takes `stock(conv, x)` -- what the module did
+    _sn_hooks_by_hand: spectral norm's pre-hook is called by hand, a module with any other hook takes `stock(conv, x)` -- what the module did
     without this mode.  So does every conv or input outside what the kernels are meant for (bias, other geometry, in_channels % 64,
     out_channels % 64, CPU tensors): % 64 is the module's gate as in _disc_conv4x4s2, it keeps the 8-feature net of fixture g14 on what it runs
     today (the kernels themselves take in_channels % 32 and 32 output channels, include/srbh.h)."""
-    from torch.nn.utils.spectral_norm import SpectralNorm
     ok = (isinstance(conv, nn.Conv2d) and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)
           and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None and conv.padding_mode == "zeros"
           and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0 and x.dim() == 4 and x.is_cuda)
-    pre = list(conv._forward_pre_hooks.values())
-    if (not ok or any(not isinstance(h, SpectralNorm) for h in pre) or conv._forward_hooks or conv._backward_hooks or conv._backward_pre_hooks
-            or getattr(conv, "_forward_pre_hooks_with_kwargs", None) or getattr(conv, "_forward_hooks_with_kwargs", None)):
+    if not ok or not _sn_hooks_by_hand(conv, x):
         return stock(conv, x)
-    for hook in pre:
-        hook(conv, (x,))
     return _DiscConvWideFn.apply(x, conv.weight)
 
 
@@ -597,24 +596,6 @@ class _PlanePool:
             b = self.bufs[k] = torch.zeros(_lib.lib().srbh_act16_bytes(self.B, chunks * 32, H, W), dtype=torch.uint8, device=self.device)
         wcache.keep(b)
         return b
-
-
-def _wconv(inp, in_chunks, w, bias, cout, B, H, W, bf16=0, relu=0, mask=None, add=None, out16=None, out32=None, out32_c=0):
-    import ctypes as C
-    from . import _lib
-    a = _lib.WConvArgs()
-    a.in_, a.in_chunks_total, a.in_chunk0, a.in_chunks = inp.data_ptr(), in_chunks, 0, in_chunks
-    a.w, a.bias, a.cout = w.data_ptr(), (None if bias is None else bias.data_ptr()), cout
-    a.B, a.H, a.W, a.bf16, a.relu = B, H, W, bf16, relu
-    if mask is not None:
-        a.mask16, a.mask_chunks_total, a.mask_chunk0 = mask.data_ptr(), cout // 32, 0
-    if add is not None:
-        a.add16, a.add_chunks_total, a.add_chunk0 = add.data_ptr(), cout // 32, 0
-    if out16 is not None:
-        a.out16, a.out16_chunks_total, a.out16_chunk0 = out16.data_ptr(), cout // 32, 0
-    if out32 is not None:
-        a.out32, a.out32_c = out32.data_ptr(), out32_c
-    _lib.check(_lib.lib().srbh_wconv3x3(C.byref(a), _lib.stream_ptr()), "wconv3x3(vgg)")
 
 
 class _PerceptualFn(torch.autograd.Function):
