@@ -743,6 +743,26 @@ int srbh_label_prep(const unsigned char* height, int B, int H, int W, const unsi
                     float* weight_aggre, void* stream);
 int srbh_normalize_clamp(const float* src, float* dst, int B, int C, int H, int W, const float* mins, const float* ranges,
                          float lo, float hi, int clamp, void* stream);
+/* Training augmentation of both datasets (BH_loader.py:356-359 in myImageFloder_S12_globe, :735-737 in myImageFloderLRHRglobe:
+ * Compose([Flip, RandomGridShuffle(grid=(2, 2)), Rotate]), applied before the normalisation at :361-369 / :744-750, the x0.25
+ * decimation at :365 and the label branch at :373-392).  The definition is DESIGN.md 3.x; the per-image parameters are device arrays
+ * (Python: loader_math.Augment.to_device):
+ *   flip   int32 [B]                  bit 0 reverses the columns, bit 1 the rows (only the low two bits are read);
+ *   perm   int32 [B][4]               source cell of destination cell i, cells row-major (only the low two bits are read; 16-byte aligned);
+ *   tables int32 [B][2 Wg + 2 Hg]     ax[Wg], bx[Wg], X0[Hg], Y0[Hg]: the inverse rotation in 2^-10 fixed point (16-byte aligned).
+ * aug_image: src fp32 [B][C][Hs][Ws] holds the grid at 1/up (grid Hg x Wg = Hs up x Ws up, multiples of 8); dst fp32
+ *   [B][C][Hg/step][Wg/step] is the bilinear REFLECT_101 sample of the augmented grid at (step j, step i), then
+ *   clip((v - mins[c]) / ranges[c], lo, hi) as normalize_clamp (mins == ranges == NULL: no normalisation; clip only when clamp != 0).
+ *   up 4 / step 4 is the LR tile (:353-365), up 1 / step 1 the SR stage's HR image (:735-750), up 4 / step 1 the augmented x4 image.
+ * aug_label_prep: the nearest-sampled augmented uint8 label [B][H][W] fused with label_prep's five outputs; label_out (optional,
+ *   4-byte aligned) receives the augmented label itself.
+ * Refused with SRBH_ERR_ARG: null pointers, a grid side that is no multiple of 8 or above 32768, up or step < 1, a step that does not
+ * divide the grid.  Flip codes and perms live on the device and are refused by the Python layer; the kernels mask them. */
+int srbh_aug_image(const float* src, int B, int C, int Hs, int Ws, int up, float* dst, int step, const int* flip, const int* perm,
+                   const int* tables, const float* mins, const float* ranges, float lo, float hi, int clamp, void* stream);
+int srbh_aug_label_prep(const unsigned char* height, int B, int H, int W, const int* flip, const int* perm, const int* tables,
+                        const unsigned char* buildhir_lut, const float* class_weight, long long* build, float* height_f,
+                        float* weight, float* height_aggre, float* weight_aggre, unsigned char* label_out, void* stream);
 
 /* ---- loss and metric reductions ------------------------------------------------------------
  * Replace the elementwise / reduction passes of reference losses_pytorch/selfloss.py and metrics.py.  All outputs are

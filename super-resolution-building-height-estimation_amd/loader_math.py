@@ -9,7 +9,8 @@ import torch
 
 from . import _lib
 
-__all__ = ["hierweight", "hierweight_simple", "hierweight_equal", "LabelPrep", "normalize_tiles"]
+__all__ = ["hierweight", "hierweight_simple", "hierweight_equal", "LabelPrep", "normalize_tiles", "Augment", "AugmentParams",
+           "DeviceAugment", "train_batch", "sr_pair"]
 
 
 def _class_freq(stats, hir):
@@ -80,3 +81,197 @@ def normalize_tiles(img, mins, maxs, datarange=(0, 1)):
     _lib.check(_lib.lib().srbh_normalize_clamp(x.data_ptr(), out.data_ptr(), B, Cc, Hh, Ww, mn.data_ptr(), rg.data_ptr(),
                                                float(lo), float(hi), int(clamp), _lib.stream_ptr()), "normalize_clamp")
     return out
+
+
+# ---- training augmentation on the device (BH_loader.py:356-359, :735-737; definition: DESIGN.md 3.x) ------------------------------
+_IDENTITY_PERM = (0, 1, 2, 3)
+_FIX = 1024.0               # the rotation's coordinates are 2^-10 fixed point
+_MAX_GRID = 32768           # as libsrbh's check: |coordinate| * 1024 stays far inside int32
+
+
+class AugmentParams:
+    """One batch's augmentation as CPU tensors: ``flip`` (B,) int32 codes 0..3 (bit 0 reverses the columns, bit 1 the rows), ``perm``
+    (B, 4) int32 (source cell of destination cell i; cells row-major), ``angle`` (B,) float64 degrees counter-clockwise and ``rotate``
+    (B,) bool (False: that image is not rotated whatever its angle).  ``Augment.draw`` makes one; tests build them from explicit values."""
+
+    def __init__(self, flip, perm, angle, rotate=None):
+        self.flip = torch.as_tensor(flip, dtype=torch.int32).reshape(-1).contiguous()
+        B = self.flip.numel()
+        self.perm = torch.as_tensor(perm, dtype=torch.int32).reshape(-1, 4).contiguous()
+        self.angle = torch.as_tensor(angle, dtype=torch.float64).reshape(-1).contiguous()
+        self.rotate = (torch.ones(B, dtype=torch.bool) if rotate is None else torch.as_tensor(rotate, dtype=torch.bool).reshape(-1)).contiguous()
+        for t in (self.flip, self.perm, self.angle, self.rotate):
+            if t.is_cuda:
+                raise ValueError("AugmentParams: the parameters are CPU tensors (Augment.to_device uploads them)")
+        if not (self.perm.shape[0] == B and self.angle.numel() == B and self.rotate.numel() == B):
+            raise ValueError(f"AugmentParams: flip, perm, angle and rotate must describe the same {B} images")
+        if B and (int(self.flip.min()) < 0 or int(self.flip.max()) > 3):
+            raise ValueError("AugmentParams: a flip code is 0 (none), 1 (columns), 2 (rows) or 3 (both)")
+        if B and not bool((self.perm.sort(dim=1).values == torch.arange(4, dtype=torch.int32)).all()):
+            raise ValueError("AugmentParams: every perm row must be a permutation of 0..3")
+        if not bool(torch.isfinite(self.angle).all()):
+            raise ValueError("AugmentParams: angles must be finite")
+
+    def __len__(self):
+        return self.flip.numel()
+
+    @classmethod
+    def identity(cls, B):
+        return cls(torch.zeros(B, dtype=torch.int32), torch.tensor(_IDENTITY_PERM, dtype=torch.int32).repeat(B, 1),
+                   torch.zeros(B, dtype=torch.float64), torch.zeros(B, dtype=torch.bool))
+
+
+class DeviceAugment:
+    """``AugmentParams`` for one grid size on the device: int32 ``flip`` (B,), ``perm`` (B, 4), ``tables`` (B, 2 Wg + 2 Hg) and the fp32
+    ``consts`` that rode along, all views of ONE device buffer that one copy filled."""
+
+    def __init__(self, B, Hg, Wg, flip, perm, tables, consts):
+        self.B, self.Hg, self.Wg = B, Hg, Wg
+        self.flip, self.perm, self.tables, self.consts = flip, perm, tables, consts
+
+
+class Augment:
+    """The reference's ``A.Compose([A.Flip(p=0.5), A.RandomGridShuffle(grid=(2, 2), p=0.5), A.Rotate(p=0.5)])`` (BH_loader.py:62-66,
+    :713-716) as parameters for libsrbh's gather kernels.  The transforms are DEFINED in DESIGN.md 3.x: modelled on what albumentations
+    and cv2 are understood to do, not tested against either (neither is available), and albumentations' random stream is not matched."""
+
+    def __init__(self, grid=(2, 2), limit=90, p_flip=0.5, p_shuffle=0.5, p_rotate=0.5):
+        if tuple(grid) != (2, 2):
+            raise NotImplementedError(f"Augment: only grid=(2, 2) is supported (got {tuple(grid)})")
+        self.grid, self.limit = (2, 2), float(limit)
+        self.p_flip, self.p_shuffle, self.p_rotate = float(p_flip), float(p_shuffle), float(p_rotate)
+
+    def draw(self, B, generator):
+        """each step independently with its probability: a flip code uniform on {1, 2, 3}, a uniform permutation of the four cells (the
+        identity included), an angle uniform on [-limit, limit).  `generator`: a CPU torch.Generator, so a seed reproduces a run."""
+        if generator.device.type != "cpu":
+            raise ValueError("Augment.draw: a CPU torch.Generator (the parameters are made on the host)")
+        u = torch.rand((B, 3), generator=generator, dtype=torch.float64)
+        code = torch.randint(1, 4, (B,), generator=generator, dtype=torch.int32)
+        perm = torch.rand((B, 4), generator=generator, dtype=torch.float64).argsort(dim=1).to(torch.int32)
+        angle = (torch.rand((B,), generator=generator, dtype=torch.float64) * 2.0 - 1.0) * self.limit
+        do_flip, do_shuffle, do_rotate = u[:, 0] < self.p_flip, u[:, 1] < self.p_shuffle, u[:, 2] < self.p_rotate
+        flip = torch.where(do_flip, code, torch.zeros_like(code))
+        perm = torch.where(do_shuffle[:, None], perm, torch.tensor(_IDENTITY_PERM, dtype=torch.int32).expand(B, 4))
+        angle = torch.where(do_rotate, angle, torch.zeros_like(angle))
+        return AugmentParams(flip, perm, angle, do_rotate)
+
+    @staticmethod
+    def _check_grid(Hg, Wg):
+        if Hg <= 0 or Wg <= 0 or Hg % 8 or Wg % 8 or Hg > _MAX_GRID or Wg > _MAX_GRID:
+            raise ValueError(f"Augment: the grid {Hg} x {Wg} must be multiples of 8, at most {_MAX_GRID} a side")
+
+    def tables(self, params, Hg, Wg):
+        """(B, 2 Wg + 2 Hg) int32 numpy: per image ax[Wg], bx[Wg], X0[Hg], Y0[Hg] of the inverse rotation about the pixel-centre
+        point ((Wg-1)/2, (Hg-1)/2), float64 on the host, rounded to nearest-even at 2^-10.  An image that is not rotated gets the
+        identity tables, which give back every pixel exactly with fraction 0."""
+        self._check_grid(Hg, Wg)
+        ang = np.radians(np.where(params.rotate.numpy(), params.angle.numpy(), 0.0))
+        a, b = np.cos(ang)[:, None], np.sin(ang)[:, None]
+        cx, cy = (Wg - 1) / 2.0, (Hg - 1) / 2.0
+        m0, m1, m2 = a, -b, cx - a * cx + b * cy
+        m3, m4, m5 = b, a, cy - b * cx - a * cy
+        x, y = np.arange(Wg, dtype=np.float64)[None, :], np.arange(Hg, dtype=np.float64)[None, :]
+        t = np.concatenate([np.rint(m0 * x * _FIX), np.rint(m3 * x * _FIX), np.rint((m1 * y + m2) * _FIX), np.rint((m4 * y + m5) * _FIX)], axis=1)
+        return t.astype(np.int32)
+
+    def to_device(self, params, Hg, Wg, device, consts=()):
+        """Upload one batch's parameters for an Hg x Wg grid: one pinned staging buffer, one non_blocking copy, no host synchronisation
+        (the thread that prepares a batch is the thread that queues the training step's launches: see harness._label_consts).  `consts`:
+        float vectors (the bands' mins / ranges) that ride in the same copy and come back as fp32 device views.  The pinned buffer is a
+        fresh one per batch from torch's caching host allocator, which hands it out again only after the copy has run."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("Augment.to_device (libsrbh): device tensors only -- there is no CPU path")
+        B, T = len(params), 2 * Wg + 2 * Hg
+        tab = self.tables(params, Hg, Wg)
+        cs = [np.ascontiguousarray(c, dtype=np.float32).reshape(-1) for c in consts]
+        n_t, n_p = B * T, B * 4                  # tables first, then perm: both stay 16-byte aligned (T % 16 == 0)
+        offs = np.cumsum([0, n_t, n_p, (B + 3) // 4 * 4] + [(c.size + 3) // 4 * 4 for c in cs]).tolist()
+        stage = torch.empty((int(offs[-1]),), dtype=torch.int32, pin_memory=True)
+        host = stage.numpy()
+        host[:n_t] = tab.reshape(-1)
+        host[n_t:n_t + n_p] = params.perm.numpy().reshape(-1)
+        host[offs[2]:offs[2] + B] = params.flip.numpy()
+        for c, o in zip(cs, offs[3:]):
+            host[o:o + c.size] = c.view(np.int32)
+        dev = stage.to(device, non_blocking=True)
+        views = [dev[o:o + c.size].view(torch.float32) for c, o in zip(cs, offs[3:])]
+        return DeviceAugment(B, Hg, Wg, dev[offs[2]:offs[2] + B], dev[n_t:n_t + n_p].view(B, 4), dev[:n_t].view(B, T), views)
+
+
+_AUGMENT = Augment()
+
+
+def _aug_image(x, up, step, dp, mins, ranges, datarange, what):
+    """x (B,C,Hs,Ws) fp32 device tensor -> the augmented grid (Hs up x Ws up) sampled every `step` pixels, normalised when mins is given"""
+    B, Cc, Hs, Ws = x.shape
+    if (B, Hs * up, Ws * up) != (dp.B, dp.Hg, dp.Wg):
+        raise ValueError(f"{what}: parameters made for {dp.B} images of {dp.Hg} x {dp.Wg}, tensor is {B} x {Hs * up} x {Ws * up}")
+    out = torch.empty((B, Cc, Hs * up // step, Ws * up // step), dtype=torch.float32, device=x.device)
+    clamp = mins is not None and isinstance(datarange, tuple)
+    lo, hi = (datarange if clamp else (0.0, 0.0))
+    _lib.check(_lib.lib().srbh_aug_image(x.data_ptr(), B, Cc, Hs, Ws, up, out.data_ptr(), step, dp.flip.data_ptr(), dp.perm.data_ptr(),
+                                         dp.tables.data_ptr(), None if mins is None else mins.data_ptr(),
+                                         None if mins is None else ranges.data_ptr(), float(lo), float(hi), int(clamp),
+                                         _lib.stream_ptr()), what)
+    return out
+
+
+def _f32_image(t, what):
+    if not (t.is_cuda and t.dim() == 4):
+        raise RuntimeError(f"{what} (libsrbh): expects (B,C,H,W) device tensors -- there is no CPU path")
+    return t.detach().float().contiguous()
+
+
+def _band_consts(mins, maxs, Cc, what):
+    mn, rg = np.asarray(mins), np.asarray(maxs) - np.asarray(mins)
+    if mn.shape != (Cc,) or rg.shape != (Cc,):
+        raise ValueError(f"{what}: mins / maxs must hold one value per band ({Cc})")
+    return mn, rg
+
+
+def train_batch(raw_img, height_u8, mins, maxs, prep, params=None, datarange=(0, 1)):
+    """One height-stage training batch from raw tensors on the device, as myImageFloder_S12_globe.__getitem__ makes it
+    (BH_loader.py:353-392): raw_img (B,C,h,w) fp32 raw bands, height_u8 (B,4h,4w) uint8 labels, `prep` a LabelPrep.  Returns
+    (lr, height, height_aggre, build, weight, weight_aggre) -- what harness.synthetic_batch_device returns and TrainStep consumes.
+    `params`: AugmentParams (Augment.draw); None is the un-augmented batch, through the same kernels with identity parameters."""
+    x = _f32_image(raw_img, "train_batch")
+    if not (height_u8.is_cuda and height_u8.dtype == torch.uint8 and height_u8.dim() == 3):
+        raise RuntimeError("train_batch (libsrbh): expects a (B,H,W) uint8 device tensor of labels -- there is no CPU path")
+    B, Cc, Hs, Ws = x.shape
+    h = height_u8.contiguous()
+    if tuple(h.shape) != (B, 4 * Hs, 4 * Ws):
+        raise ValueError(f"train_batch: labels {tuple(h.shape)} do not match the x4 grid of tiles {tuple(x.shape)}")
+    Hg, Wg = 4 * Hs, 4 * Ws
+    if params is None:
+        params = AugmentParams.identity(B)
+    dp = _AUGMENT.to_device(params, Hg, Wg, x.device, _band_consts(mins, maxs, Cc, "train_batch"))
+    lr = _aug_image(x, 4, 4, dp, dp.consts[0], dp.consts[1], datarange, "aug_image")
+    dev = x.device
+    build = torch.empty((B, Hg, Wg), dtype=torch.int64, device=dev)
+    hf = torch.empty((B, Hg, Wg), dtype=torch.float32, device=dev)
+    wt = torch.empty((B, Hg, Wg), dtype=torch.float32, device=dev)
+    ha = torch.empty((B, Hs, Ws), dtype=torch.float32, device=dev)
+    wa = torch.empty((B, Hs, Ws), dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().srbh_aug_label_prep(h.data_ptr(), B, Hg, Wg, dp.flip.data_ptr(), dp.perm.data_ptr(), dp.tables.data_ptr(),
+                                              prep.lut.data_ptr(), prep.cw.data_ptr(), build.data_ptr(), hf.data_ptr(), wt.data_ptr(),
+                                              ha.data_ptr(), wa.data_ptr(), None, _lib.stream_ptr()), "aug_label_prep")
+    return lr, hf, ha, build, wt, wa
+
+
+def sr_pair(raw_lr, raw_hr, lr_mins, lr_maxs, hr_mins, hr_maxs, params, datarange=(0, 1)):
+    """One SR-stage training pair as myImageFloderLRHRglobe.__getitem__ makes it (BH_loader.py:731-750): raw_lr (B,C,h,w) and raw_hr
+    (B,C',4h,4w) fp32 raw values -> (lq, gt) for RealESRGAN.feed_data; both get the same augmentation, lq is clipped to `datarange`,
+    gt is not (:747-750).  `params` None: no augmentation."""
+    lr, hr = _f32_image(raw_lr, "sr_pair"), _f32_image(raw_hr, "sr_pair")
+    B, Cl, Hs, Ws = lr.shape
+    if (hr.shape[0], hr.shape[2], hr.shape[3]) != (B, 4 * Hs, 4 * Ws):
+        raise ValueError(f"sr_pair: HR {tuple(hr.shape)} is not the x4 grid of LR {tuple(lr.shape)}")
+    if params is None:
+        params = AugmentParams.identity(B)
+    consts = _band_consts(lr_mins, lr_maxs, Cl, "sr_pair") + _band_consts(hr_mins, hr_maxs, hr.shape[1], "sr_pair")
+    dp = _AUGMENT.to_device(params, 4 * Hs, 4 * Ws, lr.device, consts)
+    lq = _aug_image(lr, 4, 4, dp, dp.consts[0], dp.consts[1], datarange, "aug_image")
+    gt = _aug_image(hr, 1, 1, dp, dp.consts[2], dp.consts[3], None, "aug_image")
+    return lq, gt
