@@ -763,6 +763,28 @@ int srbh_aug_image(const float* src, int B, int C, int Hs, int Ws, int up, float
 int srbh_aug_label_prep(const unsigned char* height, int B, int H, int W, const int* flip, const int* perm, const int* tables,
                         const unsigned char* buildhir_lut, const float* class_weight, long long* build, float* height_f,
                         float* weight, float* height_aggre, float* weight_aggre, unsigned char* label_out, void* stream);
+/* Inference tiles cut and normalised from a city's device rasters (BH_loader.py:933-993, gridimgLoader.__getitem__: two window reads,
+ * the band cut, the concatenate, the cast to float32 and (v - min) / (max - min) per band WITHOUT a clip -- one grid cell at a time
+ * there, a batch of cells per launch here).
+ *   srcA  [CA][H][W] of element type typeA (Sentinel-2), of which the first CA_used bands are taken (:958, :971);
+ *   srcB  [CB][H][W] of element type typeB (Sentinel-1), all bands; NULL with CB = 0 for a tile of srcA's bands alone;
+ *   pos   int32 [N][4] on the device: (xoff, yoff, xcount, ycount) in raster pixels;
+ *   mins, ranges  fp32 [CA_used + CB] on the device (range = max - min, formed in float64 on the host as for normalize_clamp);
+ *   dst   fp32 [N][CA_used + CB][tile][tile], 16-byte aligned; tile a multiple of 4, at most 256.
+ * dst[n][c][j][i] = ((float)src_c[yoff + j][xoff + i] - mins[c]) / ranges[c]  where i < xcount, j < ycount AND the source pixel lies
+ * inside the raster: normalize_clamp's two fp32 operations in its order (true division), the conversion to float exact for every type.
+ * Everywhere else dst is +0.0f.  The zero fill is this project's own choice (the reference cannot batch a clipped window): it is the
+ * zero padding predict_tiles gives a ragged batch, and the mosaic reads [:ycount, :xcount] of a tile's prediction only.  The
+ * inside-the-raster test is part of the predicate, so no content of pos takes a load outside [0, C*H*W) of either source; offsets
+ * are 64-bit (C*H*W of a large city exceeds 2^31).  Every element of dst is written, by one 16-byte store per four pixels.
+ * Refused with SRBH_ERR_ARG: null srcA / pos / dst / mins / ranges; srcB and CB that disagree; an unknown type code; CA_used outside
+ * 1..CA; N, H or W <= 0; tile < 4, no multiple of 4 or above 256; a dst that is not 16-byte aligned; too many workgroups.  The
+ * windows live on the device: the Python layer (loader_math.check_windows) validates them. */
+#define SRBH_GRID_F32 0
+#define SRBH_GRID_U16 1
+#define SRBH_GRID_I16 2
+int srbh_grid_tiles(const void* srcA, int typeA, int CA, int CA_used, const void* srcB, int typeB, int CB, int H, int W,
+                    const int* pos, int N, const float* mins, const float* ranges, float* dst, int tile, void* stream);
 
 /* ---- loss and metric reductions ------------------------------------------------------------
  * Replace the elementwise / reduction passes of reference losses_pytorch/selfloss.py and metrics.py.  All outputs are

@@ -348,6 +348,7 @@ SIGNATURES = {
     "srbh_normalize_clamp": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _f, _i, _vp]),
     "srbh_aug_image": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _vp]),
     "srbh_aug_label_prep": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "srbh_grid_tiles": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp]),
     "srbh_rrdbnet_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "srbh_rrdbnet_last_status": (_i, [_vp, _i, _i, _i, _i, _vp]),
     "srbh_rrdbnet_trunk_out": (_i, [_vp, _sz, _i, _i, _i, _i, _i, _vp, _vp]),

@@ -20,6 +20,10 @@
 //                    channels; consecutive lanes store consecutive x.  Bilinear, then (v - min) / range and the clip.
 // aug_label_prep_kernel : one thread per 4x4 cell as label_prep_kernel, each label pixel a nearest sample.
 // Every index is folded / masked on the device, so no content of the parameter arrays can take a read outside the source.
+//
+// Inference tiles (:933-993, gridimgLoader.__getitem__): grid_tiles_kernel cuts a batch of windows out of a city's two device rasters
+// (uint16 / int16 / float32, channel-major), concatenates the bands and normalises as normalize_clamp_kernel does, without the clip;
+// outside the window, and outside the raster, a tile is +0.0f.
 #include "srbh_internal.h"
 
 namespace {
@@ -202,7 +206,68 @@ __global__ void aug_label_prep_kernel(const unsigned char* __restrict__ height, 
 
 constexpr int AUG_MAX_GRID = 32768;      // |coordinate| * 1024 stays far inside int32 (the sampling position overshoots by < 1.5 N)
 
+// ---- inference tiles from a city's rasters (BH_loader.py:933-993) ------------------------------------------------------------------
+// One element of a raster as float: exact for all three types (16-bit integers fit fp32's 24-bit significand).
+__device__ __forceinline__ float grid_load(const void* src, int type, long long o) {
+    if (type == SRBH_GRID_U16) return (float)((const unsigned short*)src)[o];
+    if (type == SRBH_GRID_I16) return (float)((const short*)src)[o];
+    return ((const float*)src)[o];
+}
+
+// One thread: four consecutive pixels of one tile row, one 16-byte store (tile % 4 == 0: a store never straddles rows).  Consecutive
+// lanes read consecutive groups of four source pixels of the same raster row.  A pixel is loaded only when it lies in the window AND in
+// the raster -- whatever pos holds, no load leaves the source; the window arithmetic is 64-bit so that no content of pos overflows it.
+__global__ void __launch_bounds__(256) grid_tiles_kernel(const void* __restrict__ srcA, int typeA, int CA_used,
+                                                         const void* __restrict__ srcB, int typeB, int CB, int H, int W,
+                                                         const int* __restrict__ pos, int N, const float* __restrict__ mins,
+                                                         const float* __restrict__ ranges, float* __restrict__ dst, int tile) {
+    const int q = tile / 4, C = CA_used + CB;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)N * C * tile * q) return;
+    const int i0 = (int)(idx % q) * 4;
+    long long r = idx / q;
+    const int j = (int)(r % tile);
+    r /= tile;
+    const int c = (int)(r % C);
+    const int* p = pos + 4 * (r / C);
+    const int xoff = p[0], yoff = p[1], xcount = p[2], ycount = p[3];
+    const long long y = (long long)yoff + j;
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (j < ycount && y >= 0 && y < H) {
+        const bool a = c < CA_used;
+        const void* src = a ? srcA : srcB;
+        const int type = a ? typeA : typeB;
+        const long long row = ((long long)(a ? c : c - CA_used) * H + y) * W;
+        const float mn = mins[c], rg = ranges[c];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const long long x = (long long)xoff + i0 + k;
+            if (i0 + k < xcount && x >= 0 && x < W) v[k] = (grid_load(src, type, row + x) - mn) / rg;
+        }
+    }
+    *(float4*)(dst + idx * 4) = make_float4(v[0], v[1], v[2], v[3]);
+}
+
 }  // namespace
+
+extern "C" int srbh_grid_tiles(const void* srcA, int typeA, int CA, int CA_used, const void* srcB, int typeB, int CB, int H, int W,
+                               const int* pos, int N, const float* mins, const float* ranges, float* dst, int tile, void* stream) {
+    SRBH_REQUIRE(srcA && pos && dst && mins && ranges, "srbh_grid_tiles: null pointer");
+    SRBH_REQUIRE(CB >= 0 && (srcB != nullptr) == (CB > 0), "srbh_grid_tiles: srcB and CB=%d must both be given or both be absent", CB);
+    SRBH_REQUIRE(typeA >= SRBH_GRID_F32 && typeA <= SRBH_GRID_I16 && (!srcB || (typeB >= SRBH_GRID_F32 && typeB <= SRBH_GRID_I16)),
+                 "srbh_grid_tiles: unknown element type typeA=%d typeB=%d (0 float32, 1 uint16, 2 int16)", typeA, typeB);
+    SRBH_REQUIRE(CA_used >= 1 && CA_used <= CA, "srbh_grid_tiles: CA_used=%d must lie in 1..CA=%d", CA_used, CA);
+    SRBH_REQUIRE(N > 0 && H > 0 && W > 0, "srbh_grid_tiles: bad geometry N=%d H=%d W=%d", N, H, W);
+    SRBH_REQUIRE(tile >= 4 && tile % 4 == 0 && tile <= 256, "srbh_grid_tiles: tile=%d must be a multiple of 4 in 4..256", tile);
+    SRBH_REQUIRE(((uintptr_t)dst & 15) == 0, "srbh_grid_tiles: dst must be 16-byte aligned");
+    const long long per_tile = ((long long)CA_used + CB) * tile * (tile / 4);      // threads per tile: below 2^47
+    SRBH_REQUIRE(N <= 0x7fffffffLL * 256 / per_tile, "srbh_grid_tiles: too many workgroups");
+    const long long total = N * per_tile;
+    hipLaunchKernelGGL(grid_tiles_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, srcA, typeA, CA_used,
+                       srcB, typeB, CB, H, W, pos, N, mins, ranges, dst, tile);
+    SRBH_HIP(hipGetLastError());
+    return SRBH_OK;
+}
 
 extern "C" int srbh_aug_image(const float* src, int B, int C, int Hs, int Ws, int up, float* dst, int step, const int* flip,
                               const int* perm, const int* tables, const float* mins, const float* ranges, float lo, float hi,

@@ -829,6 +829,27 @@ def predict_tiles(net_hr, model, tiles, posall, mosaic, batch=32, rank=0, world=
 
 
 @torch.no_grad()
+def predict_city(net_hr, model, s2, s1, pos, s2_stats, s1_stats, nchans=6, chans_build=7, batch=32, rank=0, world=1, dist=None,
+                 pad_to=None):
+    """predict_whole_image_grid (predict_realesanet_feature_globe.py:138-210) without the GeoTIFF IO: a city goes in as its two device
+    rasters ``s2`` (C2, H, W) and ``s1`` (C1, H, W) of uint16, int16 or float32, its grid windows ``pos`` (N, 4) in raster pixels
+    (loader_math.grid_windows, or the cells of the city's grid file) and the (2, C) min / max stats, and comes out as the
+    (height uint16, building class uint8) rasters of 4 H x 4 W on the device.  The tiles exist one batch at a time
+    (loader_math.GridTiles); predict_tiles runs unchanged.  With ``dist`` the ranks' shards are summed into rank 0
+    (Mosaic.reduce_to_), which returns the rasters; the other ranks return None."""
+    from .loader_math import GridTiles
+    from .mosaic import Mosaic
+    tiles = GridTiles(s2, s1, pos, s2_stats, s1_stats, nchans=nchans)
+    mosaic = Mosaic(4 * s2.shape[1], 4 * s2.shape[2], chans_build, s2.device)
+    predict_tiles(net_hr, model, tiles, tiles.pos, mosaic, batch=batch, rank=rank, world=world, pad_to=pad_to)
+    if dist is not None:
+        mosaic.reduce_to_(dist, dst=0)
+        if rank != 0:
+            return None
+    return mosaic.finalize()
+
+
+@torch.no_grad()
 def evaluate_tiles(net_hr, model, tiles, height_ref, build_label, batch=32, num_class=7, ref_batch=1, rank=0, world=1, keep_maps=False):
     """The validation / test loops of the reference (train.py:315-344 vtest_epoch, :427-486 vtest_epoch2) for this rank's shard of a tile
     set, with predict_tiles' batching and an evaluation in the place of the mosaic: RRDBNet feature extraction -> height / building

@@ -1,7 +1,8 @@
 """Loader-side tensor math on the device (reference BH_loader.py:30-61,326-329,361-392).
 
 ``hierweight*`` are the (tiny, host-side) class-weight formulas; ``LabelPrep`` / ``normalize_tiles`` are libsrbh
-kernels that turn a batch of raw uint8 height labels / raw band values into the tensors the training step consumes."""
+kernels that turn a batch of raw uint8 height labels / raw band values into the tensors the training step consumes;
+``GridTiles`` cuts and normalises the inference tiles of a city from its two device rasters, one batch per launch."""
 from __future__ import annotations
 
 import numpy as np
@@ -10,7 +11,7 @@ import torch
 from . import _lib
 
 __all__ = ["hierweight", "hierweight_simple", "hierweight_equal", "LabelPrep", "normalize_tiles", "Augment", "AugmentParams",
-           "DeviceAugment", "train_batch", "sr_pair"]
+           "DeviceAugment", "train_batch", "sr_pair", "grid_windows", "check_windows", "GridTiles"]
 
 
 def _class_freq(stats, hir):
@@ -275,3 +276,126 @@ def sr_pair(raw_lr, raw_hr, lr_mins, lr_maxs, hr_mins, hr_maxs, params, datarang
     lq = _aug_image(lr, 4, 4, dp, dp.consts[0], dp.consts[1], datarange, "aug_image")
     gt = _aug_image(hr, 1, 1, dp, dp.consts[2], dp.consts[3], None, "aug_image")
     return lq, gt
+
+
+# ---- inference tiles cut from a city's device rasters (BH_loader.py:933-993, gridimgLoader; definition: DESIGN.md 3.24) -------------
+def _grid_starts(length, cell, stride):
+    """starts k * stride below `length`; one with k > 0 is kept only if its window holds a pixel the previous window did not"""
+    return [x for x in range(0, length, stride) if x == 0 or x + cell - stride < length]
+
+
+def grid_windows(width, height, cell=64, stride=64):
+    """(N, 4) int64, row-major: the windows (xoff, yoff, xcount, ycount) of a regular grid of `cell`-sided cells every `stride` pixels over
+    a width x height raster, clipped at the right and bottom edges (count = min(cell, length - start)).  Every pixel lies in at least
+    one window; stride 48 with cell 64 is the overlapping layout of the inference workload."""
+    if not (width >= 1 and height >= 1 and cell >= 1 and 1 <= stride <= cell):
+        raise ValueError(f"grid_windows: needs width, height, cell >= 1 and 1 <= stride <= cell (got {width}, {height}, {cell}, {stride})")
+    xs, ys = _grid_starts(width, cell, stride), _grid_starts(height, cell, stride)
+    return np.array([[x, y, min(cell, width - x), min(cell, height - y)] for y in ys for x in xs], dtype=np.int64).reshape(-1, 4)
+
+
+def check_windows(pos, width, height, tile):
+    """Host-side validation of (N, 4) windows (xoff, yoff, xcount, ycount): every window is non-empty, at most `tile` a side and inside
+    the width x height raster.  Returns them as an (N, 4) int64 array; raises ValueError naming the first offending row."""
+    p = np.asarray(pos.cpu() if torch.is_tensor(pos) else pos)
+    if p.ndim != 2 or p.shape[1] != 4 or not np.issubdtype(p.dtype, np.integer):
+        raise ValueError(f"check_windows: pos must be (N, 4) integers (xoff, yoff, xcount, ycount), got {p.dtype} {p.shape}")
+    p = p.astype(np.int64)
+    off, cnt, lim = p[:, :2], p[:, 2:], np.array([width, height], dtype=np.int64)
+    bad = np.flatnonzero(((off < 0) | (cnt < 1) | (cnt > tile) | (off + cnt > lim)).any(axis=1))
+    if bad.size:
+        r = int(bad[0])
+        raise ValueError(f"check_windows: row {r} {tuple(int(v) for v in p[r])} is not a window of 1..{tile} pixels a side inside the "
+                         f"{width} x {height} raster")
+    return p
+
+
+_GRID_TYPES = {torch.float32: 0, torch.uint16: 1, torch.int16: 2}          # include/srbh.h SRBH_GRID_*
+
+
+class GridTiles:
+    """A city's inference tiles, cut and normalised from its two device rasters one batch at a time: stands where predict_tiles and
+    evaluate_tiles take ``tiles``.  ``s2`` (C2, H, W) and ``s1`` (C1, H, W) or None are device tensors of dtype uint16, int16 or float32;
+    the stats are (2, C) arrays as np.loadtxt returns them from s2_minmax.txt / s1_minmax.txt (row 0 min, row 1 max), the Sentinel-2
+    ones cut to [:, :nchans] (BH_loader.py:956-961); ``pos`` (N, 4) host windows, checked once (check_windows) and uploaded once.
+    ``gt[s:e]`` is a fresh fp32 (e - s, nchans + C1, tile, tile) device tensor made by one srbh_grid_tiles launch on the current stream:
+    (v - min) / (max - min) inside each window and +0.0 outside it.  ``.pos`` is the validated host array, the ``posall`` to pass on."""
+
+    def __init__(self, s2, s1, pos, s2_stats, s1_stats, nchans=6, tile=64):
+        for name, t in (("s2", s2), ("s1", s1)):
+            if t is None and name == "s1":
+                continue
+            if not (torch.is_tensor(t) and t.is_cuda and t.dim() == 3):
+                raise RuntimeError(f"GridTiles (libsrbh): {name} must be a (C, H, W) device tensor -- there is no CPU path")
+            if t.dtype not in _GRID_TYPES:
+                raise TypeError(f"GridTiles: {name} is {t.dtype}; the rasters are uint16, int16 or float32")
+        C2, H, W = s2.shape
+        if not 1 <= nchans <= C2:
+            raise ValueError(f"GridTiles: nchans={nchans} outside 1..{C2}, the bands of s2")
+        if s1 is not None and (tuple(s1.shape[1:]) != (H, W) or s1.device != s2.device):
+            raise ValueError(f"GridTiles: s1 {tuple(s1.shape)} on {s1.device} does not match s2's {H} x {W} raster on {s2.device}")
+        if tile < 4 or tile % 4 or tile > 256:
+            raise ValueError(f"GridTiles: tile={tile} must be a multiple of 4 in 4..256")
+        C1 = 0 if s1 is None else s1.shape[0]
+        st2 = np.asarray(s2_stats, dtype=np.float64)
+        if st2.ndim != 2 or st2.shape[0] != 2 or st2.shape[1] < nchans:
+            raise ValueError(f"GridTiles: s2_stats {st2.shape} must be (2, C) with at least nchans={nchans} columns (row 0 min, row 1 max)")
+        mins, maxs = [st2[0, :nchans]], [st2[1, :nchans]]
+        if s1 is not None:
+            st1 = np.asarray(s1_stats, dtype=np.float64)
+            st1 = st1.reshape(2, -1) if st1.ndim == 1 and st1.size == 2 else st1        # (np.loadtxt of a one-band file gives (2,))
+            if st1.ndim != 2 or st1.shape[0] != 2 or st1.shape[1] < C1:
+                raise ValueError(f"GridTiles: s1_stats {st1.shape} must be (2, C) with at least the {C1} bands of s1")
+            mins.append(st1[0, :C1])
+            maxs.append(st1[1, :C1])
+        mins, maxs = np.concatenate(mins), np.concatenate(maxs)
+        ranges = maxs - mins                                      # float64, rounded once below: as normalize_tiles
+        if not (np.isfinite(mins).all() and np.isfinite(ranges).all()) or (ranges.astype(np.float32) == 0).any():
+            raise ValueError("GridTiles: every band needs finite stats with max != min (a zero range divides by zero)")
+        try:
+            self.pos = check_windows(pos, W, H, tile)
+        except ValueError as e:
+            raise ValueError(f"GridTiles: {e}") from None
+        if self.pos.shape[0] == 0:
+            raise ValueError("GridTiles: no windows")
+        self.s2, self.s1 = s2.contiguous(), None if s1 is None else s1.contiguous()
+        self.nchans, self.tile, self.device = nchans, tile, s2.device
+        self.shape = (self.pos.shape[0], nchans + C1, tile, tile)
+        consts = torch.from_numpy(np.concatenate([mins, ranges]).astype(np.float32))
+        self._mins, self._ranges = consts.to(self.device).split(nchans + C1)
+        self._pos_dev = torch.from_numpy(self.pos.astype(np.int32)).to(self.device)
+        # The memo.  _PredictGraph's look-ahead asks for every full batch twice -- as the NEXT batch of call k and as the CURRENT batch
+        # of call k + 1 --, so a slice handed out is kept and handed out again, and it stays valid (neither rewritten nor returned to
+        # the allocator) until TWO further distinct slices have been requested; the third further one drops it.  Why that is long
+        # enough: a slice is made on the stream that is current at the request (the main stream) but as the "next" batch of call k it
+        # is read by a copy on the graph's SIDE stream.  That copy is ordered behind ev_trunk of call k, hence behind the kernel that
+        # made the slice, and in front of ev_lr[parity] recorded on the side stream right after; call k + 1 makes the main stream wait
+        # for exactly that event (cur.wait_event(ev_lr[p])) before its reg / seg graph.  The two further slices are the "next" batches
+        # of calls k + 1 and k + 2, so the slice is dropped no earlier than the request in front of call k + 2, i.e. after call
+        # k + 1 was queued whole: whatever the main stream's allocator then puts into that memory is queued behind call k + 1's
+        # wait_event and so behind the side stream's read.  As the CURRENT batch the slice is read by copies on the main stream only.
+        self._memo = []                                           # [(start, stop), tensor], oldest first, at most three
+
+    def __len__(self):
+        return self.shape[0]
+
+    def __getitem__(self, key):
+        if not isinstance(key, slice) or key.step not in (None, 1):
+            raise TypeError("GridTiles: index with a plain slice gt[s:e] (step 1)")
+        s, e, _ = key.indices(self.shape[0])
+        if e <= s:
+            return torch.empty((0,) + self.shape[1:], dtype=torch.float32, device=self.device)
+        for k, t in self._memo:
+            if k == (s, e):
+                return t
+        out = torch.empty((e - s,) + self.shape[1:], dtype=torch.float32, device=self.device)
+        s1 = self.s1
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().srbh_grid_tiles(self.s2.data_ptr(), _GRID_TYPES[self.s2.dtype], self.s2.shape[0], self.nchans,
+                                                  None if s1 is None else s1.data_ptr(), 0 if s1 is None else _GRID_TYPES[s1.dtype],
+                                                  0 if s1 is None else s1.shape[0], self.s2.shape[1], self.s2.shape[2],
+                                                  self._pos_dev[s:e].data_ptr(), e - s, self._mins.data_ptr(), self._ranges.data_ptr(),
+                                                  out.data_ptr(), self.tile, _lib.stream_ptr()), "grid_tiles")
+        self._memo.append(((s, e), out))
+        del self._memo[:-3]
+        return out
