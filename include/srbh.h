@@ -862,6 +862,40 @@ typedef struct srbh_eval_args {
 size_t srbh_eval_ws_bytes(int B, int HW, int C);
 int srbh_eval_sums(const srbh_eval_args* a, void* stream);
 
+/* ---- Dataset statistics where the data lies (reference stats_dataset_globe.py: main_stats :61-101, main_stats_buildingheight :133-159;
+ * csrc/srbh_stats.hip) --------------------------------------------------------------------------------------------------------------
+ * srbh_band_stats: src of logical shape (N, C, H, W) and element type `type` (SRBH_GRID_F32 / _U16 / _I16), read in place through the
+ * three ELEMENT strides {image, band, row} of the host array `strides` (non-negative; the column stride is 1): a batch of tiles, a band
+ * cut x[:, :6] and a crop raster[None, :, y0:y1, x0:x1] all work.  Offsets are 64-bit.  Per image n and band c, OVERWRITTEN:
+ *   stats[n][c][4] = { min, max, mean, std } float64, GDAL's order (a row stats_s1[b][i, :] of the reference's table);
+ *   count[n][c]    = the number of valid pixels, int64.
+ * A pixel is valid unless it is NaN or equals *nodata (nodata: HOST pointer to a double, NULL = none).  std is the population form
+ * sqrt(M2 / count).  count == 0 leaves four NaNs.  This is the project's own statement of what GDAL's ComputeStatistics(False) is
+ * understood to return (an exact scan of every pixel); GDAL is not available where the project is built and tested, so no result of
+ * GDAL itself has been compared.
+ * Arithmetic: float64 behind the exact conversion of each value, corrected two-pass: pass 1 gives min, max, count and the sum (mean =
+ * sum / count), pass 2 gives M2 = sum (x - mean)^2 - (sum (x - mean))^2 / count.  The error of the variance M2 / count is within
+ * 2 [(n + 2) u var + (n u)^2 (mean^2 + var)], u = 2^-53, n = count (Chan, Golub & LeVeque 1983); the mean of an integer type is the
+ * correctly rounded quotient of the exact sum.
+ * One workgroup per (image, band); a band of at most 4096 pixels is read once (kept in registers between the passes), a larger one
+ * twice.  The pixels are cut row-major into 16-byte groups, lane t of 256 adds the groups t, t + 256, ... in order, then the lanes of a
+ * wave by a shuffle tree, then the waves in wave order.  Bit-reproducible: an image's numbers depend on that image alone -- not on the
+ * run, the batch, N, or whether a group was fetched by one 16-byte load (base and strides multiples of 16 bytes) or element by element.
+ * No floating-point atomics, no workspace, one launch.
+ * Refused with SRBH_ERR_ARG: null src / strides / stats / count, an unknown type code, N, C, H or W <= 0, a negative stride,
+ * N * C above 2^31 - 1 workgroups.
+ *
+ * srbh_label_hist: hist[256] int64, OVERWRITTEN, = the exact counts of the uint8 labels (N, HW), image n at labels + n * image_stride
+ * (element stride, non-negative; a batch slice is read in place).  A workgroup counts 65536 consecutive labels of one image in 32 bits
+ * (16 labels per lane and load where base and stride are multiples of 16; runs of equal neighbours are added once, into one LDS
+ * sub-histogram per wave) and writes its slot of ws; a second kernel adds the slots into int64.  ws: srbh_label_hist_ws_bytes(N, HW)
+ * bytes of device memory (0 for arguments the call would refuse), no initialisation needed.
+ * Refused with SRBH_ERR_ARG: null labels / hist / ws, N or HW <= 0, a negative stride, more than 2^31 - 1 workgroups. */
+int srbh_band_stats(const void* src, int type, const long* strides, int N, int C, int H, int W, const double* nodata,
+                    double* stats, long long* count, void* stream);
+size_t srbh_label_hist_ws_bytes(int N, long HW);
+int srbh_label_hist(const unsigned char* labels, long image_stride, int N, long HW, long long* hist, void* ws, void* stream);
+
 /* ---- The middle of an MBConv block in ONE launch per direction (round 4; efficientnet_pytorch MBConvBlock.forward between the expand and
  * the project conv, run by smp's encoder at mymodels.py:276): BatchNorm0 (training) + SiLU -> depthwise KxK, stride 1, "same" zero padding ->
  * BatchNorm1 (training) + SiLU (+ the plane means squeeze-and-excitation pools).  fp32 NCHW, square planes 2x2 / 4x4 / 8x8, K = 3 | 5.
