@@ -944,6 +944,14 @@ int srbh_dconv_fwd_epi(const float* x, const void* wpack, float* y, int B, int C
                        const float* shift, int act, void* stream);
 size_t srbh_dconv_wgrad_ws_floats(int B, int Cin, int Cout, int H, int W);
 int srbh_dconv_wgrad(const float* x, const float* dy, float* dw, float* ws, int B, int Cin, int Cout, int H, int W, void* stream);
+/* Which kernel form the entry points above launch for a shape: host-only queries of the launchers' own planning rule, nothing is launched
+ * (tests assert the form they mean to run, and that every form the production batches select is one they compare with a reference).
+ * srbh_dconv_fwd_plan: *npx = pixels per workgroup tile (64 | 256), *mb = 16-channel output blocks per workgroup (1 | 2) of srbh_dconv_fwd /
+ * srbh_dconv_fwd_epi; chosen from (B, Cout, W) alone -- for the data gradient Cout is the forward Cin.  srbh_dconv_wgrad_plan: *mo = 16-channel
+ * output blocks per workgroup (1 | 2), *nsplit = workgroups sharing the pixels of one dW block.  SRBH_OK, or an error (nothing stored) for a
+ * null pointer or a geometry srbh_dconv_supported refuses. */
+int srbh_dconv_fwd_plan(int B, int Cout, int W, int* npx, int* mb);
+int srbh_dconv_wgrad_plan(int B, int Cin, int Cout, int W, int* mo, int* nsplit);
 
 /* ---- Adam (train.py:170-179,254-256: torch.optim.Adam over the network's parameters + the loss log_vars) as ONE launch over every parameter
  * tensor (csrc/srbh_optim.hip).  `table` (device memory): one entry per tensor -- p, m (exp_avg), v (exp_avg_sq) updated in place from the

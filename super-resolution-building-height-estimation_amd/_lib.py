@@ -329,6 +329,8 @@ SIGNATURES = {
     "srbh_dconv_fwd_epi": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "srbh_dconv_wgrad_ws_floats": (_sz, [_i, _i, _i, _i, _i]),
     "srbh_dconv_wgrad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "srbh_dconv_fwd_plan": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
+    "srbh_dconv_wgrad_plan": (_i, [_i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "srbh_pwconv_supported": (_i, [_i, _i, _i, _i]),
     "srbh_pwconv_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "srbh_pwconv_fwd_wt": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),

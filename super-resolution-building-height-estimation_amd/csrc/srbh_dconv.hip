@@ -414,6 +414,9 @@ int dispatch_fwd(const DCParams& p, const FwdPlan pl, int bf16, hipStream_t st) 
     return launch_fwd<LOGW, 64, 1>(p, bf16, st);
 }
 
+// output-channel blocks (16 each) per weight-gradient workgroup
+int wgrad_mo(int Cout) { return (Cout % 32 == 0) ? 2 : 1; }
+
 int wgrad_split(int B, int Cin, int Cout, int W, int mo) {
     // workgroups per dW block: enough to fill the chip (~1 024 waves), at least ~8 K steps of 16 pixels per wave
     const long tiles = (long)((Cout + 16 * mo - 1) / (16 * mo)) * ((Cin + 15) / 16);
@@ -475,9 +478,30 @@ static int dconv_fwd_impl(const float* x, const void* wpack, float* y, int B, in
     }
 }
 
+/* which kernel form srbh_dconv_fwd / srbh_dconv_fwd_epi launch for this shape (host only, launches nothing): *npx = pixels per workgroup
+ * tile (64 | 256), *mb = 16-channel output blocks per workgroup (1 | 2).  SRBH_OK, or an error for a geometry the convs refuse. */
+extern "C" int srbh_dconv_fwd_plan(int B, int Cout, int W, int* npx, int* mb) {
+    SRBH_REQUIRE(npx && mb, "srbh_dconv_fwd_plan: null pointer");
+    SRBH_REQUIRE(srbh_dconv_supported(B, 1, Cout, W, W), "srbh_dconv_fwd_plan: unsupported geometry B=%d Cout=%d W=%d (square planes 4..64)", B, Cout, W);
+    const FwdPlan pl = plan_fwd(B, Cout, W);
+    *npx = pl.npx;
+    *mb = pl.mb;
+    return SRBH_OK;
+}
+
+/* the same for srbh_dconv_wgrad: *mo = 16-channel output blocks per workgroup (1 | 2), *nsplit = workgroups that share the pixels of one
+ * dW block (grid.y; srbh_dconv_wgrad_ws_floats = nsplit x tiles x mo x 9 x 256) */
+extern "C" int srbh_dconv_wgrad_plan(int B, int Cin, int Cout, int W, int* mo, int* nsplit) {
+    SRBH_REQUIRE(mo && nsplit, "srbh_dconv_wgrad_plan: null pointer");
+    SRBH_REQUIRE(srbh_dconv_supported(B, Cin, Cout, W, W), "srbh_dconv_wgrad_plan: unsupported geometry B=%d Cin=%d Cout=%d W=%d", B, Cin, Cout, W);
+    *mo = wgrad_mo(Cout);
+    *nsplit = wgrad_split(B, Cin, Cout, W, *mo);
+    return SRBH_OK;
+}
+
 extern "C" size_t srbh_dconv_wgrad_ws_floats(int B, int Cin, int Cout, int H, int W) {
     if (!srbh_dconv_supported(B, Cin, Cout, H, W)) return 0;
-    const int mo = (Cout % 32 == 0) ? 2 : 1;
+    const int mo = wgrad_mo(Cout);
     const long tiles = (long)((Cout + 16 * mo - 1) / (16 * mo)) * ((Cin + 15) / 16);
     return (size_t)wgrad_split(B, Cin, Cout, W, mo) * tiles * mo * 9 * 256;
 }
@@ -487,7 +511,7 @@ extern "C" size_t srbh_dconv_wgrad_ws_floats(int B, int Cin, int Cout, int H, in
 extern "C" int srbh_dconv_wgrad(const float* x, const float* dy, float* dw, float* ws, int B, int Cin, int Cout, int H, int W, void* stream) {
     SRBH_REQUIRE(x && dy && dw && ws, "srbh_dconv_wgrad: null pointer");
     SRBH_REQUIRE(srbh_dconv_supported(B, Cin, Cout, H, W), "srbh_dconv_wgrad: unsupported geometry B=%d Cin=%d Cout=%d H=%d W=%d", B, Cin, Cout, H, W);
-    const int mo = (Cout % 32 == 0) ? 2 : 1;
+    const int mo = wgrad_mo(Cout);
     DWGParams p;
     p.x = x; p.dy = dy; p.part = ws;
     p.B = B; p.Cin = Cin; p.Cout = Cout; p.cib = (Cin + 15) / 16;

@@ -171,3 +171,18 @@ def test_inference_batchnorm_relu_in_the_conv_store(B, monkeypatch):
         b = dec(*feats)
         assert calls["n"] == 10
     assert a.shape == (B, 16, 64, 64) and rel(a, b) <= 1e-6 and float(a.min()) >= 0.0
+    # ... and against a float64 decoder (both sides above are the same conv kernel: a wrong halo row would cancel): per block nearest x2,
+    # concat, then twice the conv of the fp16-ROUNDED operands, the folded BatchNorm affine and ReLU, all in float64
+    skips = [f.cpu().double() for f in feats[1:][::-1]]
+    x = skips.pop(0)
+    for i, blk in enumerate(dec.blocks):
+        x = F.interpolate(x, scale_factor=2, mode="nearest")
+        if i < len(skips):
+            x = torch.cat([x, skips[i]], dim=1)
+        for cbr in (blk.conv1, blk.conv2):
+            conv, bn = cbr[0], cbr[1]
+            scale = bn.weight.detach().cpu().double() / (bn.running_var.cpu().double() + bn.eps).sqrt()
+            shift = bn.bias.detach().cpu().double() - bn.running_mean.cpu().double() * scale
+            x = F.conv2d(x.float().half().double(), conv.weight.detach().cpu().half().double(), None, 1, 1)
+            x = (x * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)).clamp_min(0.0)
+    assert rel(a.cpu(), x) <= 3e-3
