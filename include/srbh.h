@@ -896,6 +896,30 @@ int srbh_band_stats(const void* src, int type, const long* strides, int N, int C
 size_t srbh_label_hist_ws_bytes(int N, long HW);
 int srbh_label_hist(const unsigned char* labels, long image_stride, int N, long HW, long long* hist, void* ws, void* stream);
 
+/* ---- Per-cell built-up counts of a city's grid (reference demo_preprocess_height_v2.py: Fishgrid_stats :1143-1186, compare_twotiff_valid
+ * and compare_twotiff_valid_iou :740-933 -- one shapefile feature and two GDAL window reads at a time there, every window of a city in
+ * one launch here; csrc/srbh_cells.hip) --------------------------------------------------------------------------------------------------
+ * a, b: rasters of logical shape (H, W) and element type SRBH_GRID_U16 / _I16 / _U8, each read in place through its own ROW stride in
+ * ELEMENTS (>= W; the column stride is 1): one band of a (C, H, W) raster and a cropped view both work.  b may be NULL (one raster).
+ * pos int32 [N][4] on the device: (xoff, yoff, xcount, ycount) in raster pixels.  out int64 [N][4] on the device, OVERWRITTEN: per window
+ *   out[n] = { n_a, n_b, n_and, count }
+ * count = the window's pixels that lie inside the raster; n_a = those with f(a) > thr, n_b the same for b, n_and those where both hold
+ * (b == NULL: n_b = n_and = 0).  f is the identity (wrap8 == 0) or the value's low eight bits as an unsigned number (wrap8 == 1): the
+ * reference casts the window .astype(numpy.uint8) BEFORE it compares (:1172-1173, :790-791), so uint16 256 counts as 0 and int16 -1 as
+ * 255.  From these: Fishgrid_stats' sum = n_a, compare_twotiff_valid's vrt_sum = n_b, absdiff = n_a + n_b - 2 n_and, and the union of
+ * calculate_iou (:732-736) = n_a + n_b - n_and.  Integers only: exact, independent of any order, bit-equal between runs.
+ * One workgroup of 256 lanes per window, windows of any size; rows are cut into 16-byte groups of a's ADDRESS, the alignment taken per
+ * row; a group that lies wholly inside the raster's row is one 16-byte load with the pixels outside the window masked off, any other
+ * group is read pixel by pixel.  Every pixel is predicated on the window AND the raster, so no load touches a byte outside the rows of
+ * either raster, i.e. outside [a, a + ((H-1) * row_stride + W) * element size), whatever pos holds.  int32 partial counts per lane (hence
+ * H * W < 2^31), a shuffle tree per wave, the four waves through LDS; no atomics, no workspace, no host synchronisation, one launch.
+ * Refused with SRBH_ERR_ARG: null a / pos / out; float32 (the reference's cast of a float to uint8 is not defined outside 0..255) or an
+ * unknown type code; N, H or W <= 0; a row stride below W; H * W >= 2^31; thr outside -32768..65535; wrap8 other than 0 / 1; a raster
+ * that is not aligned to its element size.  The windows live on the device: the Python layer (city_grid.cell_counts) validates them. */
+#define SRBH_GRID_U8 3
+int srbh_cell_counts(const void* a, int typeA, long row_strideA, const void* b, int typeB, long row_strideB, int H, int W,
+                     const int* pos, int N, int thr, int wrap8, long long* out, void* stream);
+
 /* ---- The middle of an MBConv block in ONE launch per direction (round 4; efficientnet_pytorch MBConvBlock.forward between the expand and
  * the project conv, run by smp's encoder at mymodels.py:276): BatchNorm0 (training) + SiLU -> depthwise KxK, stride 1, "same" zero padding ->
  * BatchNorm1 (training) + SiLU (+ the plane means squeeze-and-excitation pools).  fp32 NCHW, square planes 2x2 / 4x4 / 8x8, K = 3 | 5.
