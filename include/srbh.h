@@ -920,6 +920,50 @@ int srbh_label_hist(const unsigned char* labels, long image_stride, int N, long 
 int srbh_cell_counts(const void* a, int typeA, long row_strideA, const void* b, int typeB, long row_strideB, int H, int W,
                      const int* pos, int N, int thr, int wrap8, long long* out, void* stream);
 
+/* ---- A city's summary: exact integer sums of a value raster under a mask raster, per window, per block and as a histogram (the step
+ * behind harness.predict_city's rasters: the reference's per-urban-centre mean and std of building height and its histogram of predicted
+ * heights, gathered there one shapefile feature and one GDAL window read at a time; csrc/srbh_summary.hip) -------------------------------
+ * v: the value raster of logical shape (H, W), element type SRBH_GRID_U16 or SRBH_GRID_U8; m: an optional mask raster (NULL: none) of
+ * the same two types.  Each is read in place through its own ROW stride in ELEMENTS (>= W; the column stride is 1).  A pixel is SELECTED
+ * when it lies inside the raster, v > vthr and (m == NULL or m > mthr); vthr and mthr lie in -1..65535 (-1 selects every value).
+ * Integers only: exact, independent of any order, bit-equal between runs; no floating point, no host synchronisation.  Rows are cut into
+ * 16-byte groups of v's ADDRESS, the alignment taken per row; a group wholly inside the raster's row is one 16-byte load with the pixels
+ * outside the rectangle at hand masked off, any other group is read pixel by pixel; m's pixels of the same columns follow the same rule
+ * with loads of element alignment.  Every load is predicated on the rectangle AND the raster: no byte outside
+ * [v, v + ((H-1) * row_strideV + W) * element size) (and the same of m) is touched, whatever pos holds.
+ * Overflow: a group's sum (16 values below 2^16) is 32-bit, everything kept across groups is 64-bit; v * v < 2^32 enters the sum of
+ * squares through a 32 x 32 -> 64-bit multiply-add, and H * W < 2^31 keeps that sum below 2^63.
+ *
+ * srbh_window_sums: pos int32 [N][4] on the device, (xoff, yoff, xcount, ycount); out int64 [N][5] on the device, OVERWRITTEN:
+ *   out[n] = { count, n, sum, sumsq, max }
+ * count = the window's pixels inside the raster, n = the selected ones among them, sum / sumsq / max = the sum of v, of v * v and the
+ * largest v over the selected pixels (all three 0 when n == 0).  Windows have any size and may overlap.  One workgroup of 256 lanes per
+ * window, a shuffle tree per wave, the four waves through LDS; one launch, no atomics, no workspace.
+ *
+ * srbh_block_sums: the raster cut into block x block blocks from the top-left corner (block >= 1; edge blocks hold what lies inside the
+ * raster), Hb = ceil(H / block), Wb = ceil(W / block); out int64 [4][Hb][Wb] on the device, planar, OVERWRITTEN: { n, sum, sumsq, max }
+ * per block.  Every block has ONE owner -- a lane for block <= 8, a wave for block <= 64, a workgroup beyond --, so the raster is read
+ * once whatever block is, nothing is added across owners, and there is no workspace.  A block larger than the raster is the raster.
+ *
+ * srbh_value_hist: hist int64 [nbins] on the device, OVERWRITTEN: the selected pixels counted by min(v / bin_width, nbins - 1), floor
+ * division (exact: (v * M) >> 32 with M = floor(2^32 / bin_width) + 1 = srbh_value_hist_magic(bin_width) equals v / bin_width for every
+ * uint16 v and every bin_width in 2..65535; bin_width 1, magic 0, takes v itself).  1 <= bin_width <= 65535, 1 <= nbins <= 4096.  At most
+ * 2048 workgroups stride over the raster, each counts into its own LDS histogram (32-bit) and stores it to its slot of ws; a second
+ * kernel adds the slots into int64 in slot order.  ws: srbh_value_hist_ws_bytes(H, W, nbins) bytes of device memory (0 for arguments the
+ * call would refuse), no initialisation needed.
+ *
+ * Refused with SRBH_ERR_ARG, nothing launched: int16, float32 or unknown type codes; null v / pos / out / hist / ws; H, W or N <= 0; a
+ * row stride below W; H * W >= 2^31; a raster not aligned to its element size; a threshold outside -1..65535; block < 1; bin_width or
+ * nbins out of range.  The windows live on the device: the Python layer (city_summary.window_sums) validates host windows. */
+int srbh_window_sums(const void* v, int typeV, long row_strideV, const void* m, int typeM, long row_strideM, int H, int W,
+                     const int* pos, int N, int vthr, int mthr, long long* out, void* stream);
+int srbh_block_sums(const void* v, int typeV, long row_strideV, const void* m, int typeM, long row_strideM, int H, int W,
+                    int block, int vthr, int mthr, long long* out, void* stream);
+unsigned srbh_value_hist_magic(int bin_width);
+size_t srbh_value_hist_ws_bytes(int H, int W, int nbins);
+int srbh_value_hist(const void* v, int typeV, long row_strideV, const void* m, int typeM, long row_strideM, int H, int W,
+                    int vthr, int mthr, int bin_width, int nbins, long long* hist, void* ws, void* stream);
+
 /* ---- The middle of an MBConv block in ONE launch per direction (round 4; efficientnet_pytorch MBConvBlock.forward between the expand and
  * the project conv, run by smp's encoder at mymodels.py:276): BatchNorm0 (training) + SiLU -> depthwise KxK, stride 1, "same" zero padding ->
  * BatchNorm1 (training) + SiLU (+ the plane means squeeze-and-excitation pools).  fp32 NCHW, square planes 2x2 / 4x4 / 8x8, K = 3 | 5.

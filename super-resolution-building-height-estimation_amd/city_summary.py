@@ -1,0 +1,221 @@
+"""What a city's predicted rasters are turned into: per-cell and per-block height sums and the height histogram, on the device.
+
+The reference publishes none of its 2.5 m rasters as the result but the step behind them: "the mean and std of building height in each
+urban center" (datasetglobe/urbanarea_meanstd.xls, README "Testing on 301 urban centers", Figure 11) and the distribution of predicted
+heights (Figure 10); its per-cell bookkeeping (``Fishgrid_stats``, ``zonal_stats``, demo_preprocess_height_v2.py:450-570, :1143-1186)
+goes one shapefile feature and one GDAL window read at a time.  Here, over ``harness.predict_city``'s ``(height uint16, class uint8)``:
+
+* ``window_sums``      per window ``[count, n, sum, sumsq, max]`` for thousands of overlapping windows in ONE libsrbh launch;
+* ``block_sums``       the same sums for every non-overlapping block x block cell, the raster read once: a 10 m / 100 m / 1 km product;
+* ``value_histogram``  the selected pixels counted by ``min(v // bin_width, nbins - 1)``;
+* ``heights_from_sums`` / ``cell_heights``  the per-cell table (n, count, fraction, mean, std, max) from those integers, on the host;
+* ``aggregate_city``   per-block rasters n, count, max, mean, fraction, density on the device;
+* ``city_summary``     the whole raster's count, n, mean, std, max, histogram and class counts.
+
+A pixel is SELECTED when it lies inside the raster, ``value > value_threshold`` and (no mask or ``mask > mask_threshold``); the defaults
+select ``height > 0`` and, with a class raster, ``build > 0``.  The kernels (csrc/srbh_summary.hip) work in integers only, so every sum
+is exact and bit-equal between runs.  Every result stays in RASTER UNITS: predict_city's height is ``round(10 h)``, so a mean of 87.3
+is 8.73 m -- nothing here divides by ten.
+
+GPU only.  Polygon zones and their rasterisation, GeoTIFFs, the .xls, float or int16 rasters and per-window class histograms are out of
+scope."""
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from .city_grid import _raster
+from .loader_math import check_windows
+
+__all__ = ["window_sums", "block_sums", "value_histogram", "heights_from_sums", "cell_heights", "aggregate_city", "city_summary"]
+
+_SUM_TYPES = {torch.uint16: 1, torch.uint8: 3}                            # include/srbh.h SRBH_GRID_U16 / _U8
+MAX_BINS = 4096
+
+
+# ---- argument handling --------------------------------------------------------------------------------------------------------------------
+# city_grid._raster's checks in another order: everything that can be judged without a device is judged first (and is testable without
+# one); the device is asked for last.
+def _one(fn, name, t):
+    if not (torch.is_tensor(t) and t.dim() == 2):
+        raise ValueError(f"{fn}: {name} must be an (H, W) tensor (got {getattr(t, 'shape', type(t))})")
+    if t.dtype not in _SUM_TYPES:
+        raise TypeError(f"{fn}: {name} is {t.dtype}; the rasters are uint16 or uint8 (int16 and float rasters are out of scope)")
+    if min(t.shape) < 1:
+        raise ValueError(f"{fn}: {name} {tuple(t.shape)} is empty")
+    if t.shape[1] > 1 and t.stride(1) != 1:
+        raise ValueError(f"{fn}: {name} has stride {t.stride(1)} along W; it must be 1 (a band or a crop is fine, a transpose is not)")
+
+
+def _rasters(fn, value, mask, value_threshold, mask_threshold):
+    """the checks that need no device: shapes, types, strides, thresholds -> (H, W, vthr, mthr)"""
+    _one(fn, "value", value)
+    H, W = value.shape
+    if mask is not None:
+        _one(fn, "mask", mask)
+        if tuple(mask.shape) != (H, W) or mask.device != value.device:
+            raise ValueError(f"{fn}: mask {tuple(mask.shape)} on {mask.device} does not match value's {H} x {W} raster on {value.device}")
+    if H * W >= 2 ** 31:
+        raise ValueError(f"{fn}: a raster of {H} x {W} pixels; counts are formed in 32 bits, so H * W must stay below 2^31")
+    vthr, mthr = int(value_threshold), int(mask_threshold)
+    if not (-1 <= vthr <= 65535 and -1 <= mthr <= 65535):
+        raise ValueError(f"{fn}: a threshold ({vthr}, {mthr}) outside -1..65535")
+    return H, W, vthr, mthr
+
+
+def _on_device(fn, value, mask):
+    """-> (value, its row stride, mask or None, its row stride), read in place; refuses host tensors"""
+    for name, t in (("value", value), ("mask", mask)):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"{fn} (libsrbh): {name} must be a device tensor -- there is no CPU path")
+    value, rs_v = _raster("value", value)                                # (types and strides are checked: this only resolves the row stride)
+    if mask is None:
+        return value, rs_v, None, 0
+    return (value, rs_v) + _raster("mask", mask)
+
+
+def _abi(value, rs_v, mask, rs_m, H, W):
+    """the eight leading arguments every entry of csrc/srbh_summary.hip takes"""
+    return (value.data_ptr(), _SUM_TYPES[value.dtype], rs_v, None if mask is None else mask.data_ptr(),
+            0 if mask is None else _SUM_TYPES[mask.dtype], rs_m, H, W)
+
+
+# ---- the kernels ----------------------------------------------------------------------------------------------------------------------------
+def window_sums(value, pos, mask=None, value_threshold=0, mask_threshold=0):
+    """-> device (N, 5) int64 ``[count, n, sum, sumsq, max]`` per window, one srbh_window_sums launch on the current stream.
+    ``value`` / ``mask``: (H, W) device tensors of uint16 or uint8, read in place (stride 1 along W, any row stride).  ``pos``: host
+    (N, 4) windows (xoff, yoff, xcount, ycount), validated to lie inside the raster and uploaded; a device int32 (N, 4) tensor is used
+    as is (the kernel sums only what lies inside the raster).  ``count`` = the window's pixels inside the raster, ``n`` = the selected
+    ones, ``sum`` / ``sumsq`` / ``max`` over the selected pixels in raster units (0 when n == 0)."""
+    H, W, vthr, mthr = _rasters("window_sums", value, mask, value_threshold, mask_threshold)
+    dev_pos = torch.is_tensor(pos) and pos.is_cuda
+    if dev_pos:
+        if pos.dtype != torch.int32 or pos.dim() != 2 or pos.shape[1] != 4 or pos.device != value.device:
+            raise ValueError(f"window_sums: a device pos must be an (N, 4) int32 tensor on {value.device} (got {pos.dtype} "
+                             f"{tuple(pos.shape)} on {pos.device})")
+        n = pos.shape[0]
+    else:
+        try:
+            p = check_windows(pos, W, H, tile=max(W, H))
+        except ValueError as e:
+            raise ValueError(f"window_sums: {e}") from None
+        n = p.shape[0]
+    if n == 0:
+        raise ValueError("window_sums: no windows")
+    value, rs_v, mask, rs_m = _on_device("window_sums", value, mask)
+    pos_dev = pos.contiguous() if dev_pos else torch.from_numpy(p.astype(np.int32)).to(value.device)
+    out = torch.empty((n, 5), dtype=torch.int64, device=value.device)
+    with torch.cuda.device(value.device):
+        _lib.check(_lib.lib().srbh_window_sums(*_abi(value, rs_v, mask, rs_m, H, W), pos_dev.data_ptr(), n, vthr, mthr, out.data_ptr(),
+                                               _lib.stream_ptr()), "srbh_window_sums")
+    return out
+
+
+def block_sums(value, block, mask=None, value_threshold=0, mask_threshold=0):
+    """-> device (4, Hb, Wb) int64 planes ``n, sum, sumsq, max`` of the block x block cells cut from the top-left corner (Hb = ceil(H /
+    block), Wb = ceil(W / block); edge blocks hold what lies inside the raster), one srbh_block_sums launch that reads each raster once.
+    Raster units."""
+    H, W, vthr, mthr = _rasters("block_sums", value, mask, value_threshold, mask_threshold)
+    block = _block("block_sums", block)
+    value, rs_v, mask, rs_m = _on_device("block_sums", value, mask)
+    out = torch.empty((4, -(-H // block), -(-W // block)), dtype=torch.int64, device=value.device)
+    with torch.cuda.device(value.device):
+        _lib.check(_lib.lib().srbh_block_sums(*_abi(value, rs_v, mask, rs_m, H, W), min(block, 2 ** 31 - 1), vthr, mthr, out.data_ptr(),
+                                              _lib.stream_ptr()), "srbh_block_sums")
+    return out
+
+
+def _block(fn, block):
+    if isinstance(block, bool) or not isinstance(block, (int, np.integer)) or block < 1:
+        raise ValueError(f"{fn}: block={block!r} must be an integer >= 1")
+    return int(block)
+
+
+def value_histogram(value, bin_width=1, nbins=256, mask=None, value_threshold=0, mask_threshold=0, workspace=None):
+    """-> device (nbins,) int64: the selected pixels counted by ``min(value // bin_width, nbins - 1)``, exact.  ``value_histogram(height,
+    10, 256, build)`` is a predicted city's histogram in the 256-bin layout of bh_stats_*.txt (one bin per metre, the last bin open);
+    ``value_histogram(build, 1, 7, value_threshold=-1)`` gives the class counts.  ``workspace``: optional device buffer of at least
+    srbh_value_hist_ws_bytes bytes to reuse between calls (its content does not matter)."""
+    H, W, vthr, mthr = _rasters("value_histogram", value, mask, value_threshold, mask_threshold)
+    for name, v, hi in (("bin_width", bin_width, 65535), ("nbins", nbins, MAX_BINS)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= hi:
+            raise ValueError(f"value_histogram: {name}={v!r} outside 1..{hi}")
+    bin_width, nbins = int(bin_width), int(nbins)
+    value, rs_v, mask, rs_m = _on_device("value_histogram", value, mask)
+    need = _lib.lib().srbh_value_hist_ws_bytes(H, W, nbins)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=value.device)
+    elif not (torch.is_tensor(workspace) and workspace.is_cuda and workspace.device == value.device and workspace.is_contiguous()
+              and workspace.numel() * workspace.element_size() >= need and workspace.data_ptr() % 4 == 0):
+        raise ValueError(f"value_histogram: workspace must be a contiguous device buffer of at least {need} bytes on {value.device}")
+    hist = torch.empty(nbins, dtype=torch.int64, device=value.device)
+    with torch.cuda.device(value.device):
+        _lib.check(_lib.lib().srbh_value_hist(*_abi(value, rs_v, mask, rs_m, H, W), vthr, mthr, bin_width, nbins, hist.data_ptr(),
+                                              workspace.data_ptr(), _lib.stream_ptr()), "srbh_value_hist")
+    return hist
+
+
+# ---- the paper's numbers from the integers ---------------------------------------------------------------------------------------------------
+def _mean_std(n, s, q):
+    """(mean, population std) of n values with sum s and sum of squares q, from Python integers: each is ONE correctly rounded division
+    (int / int is correctly rounded) -- no cancellation, however close the values lie -- and one correctly rounded square root"""
+    if n == 0:
+        return math.nan, math.nan
+    return s / n, math.sqrt((n * q - s * s) / (n * n))
+
+
+def heights_from_sums(sums):
+    """(N, 5) integers ``[count, n, sum, sumsq, max]`` (window_sums' rows, on the host) -> dict of numpy arrays, one entry per window:
+    ``n``, ``count``, ``max`` int64; ``fraction = n / count``, ``mean = sum / n`` and ``std``, the population standard deviation
+    sqrt((n sumsq - sum^2) / n^2), float64 in raster units.  n == 0 gives NaN for mean and std, count == 0 for fraction."""
+    sums = np.asarray(sums)
+    if sums.ndim != 2 or sums.shape[1] != 5 or not np.issubdtype(sums.dtype, np.integer):
+        raise ValueError(f"heights_from_sums: needs (N, 5) integers [count, n, sum, sumsq, max] (got {sums.dtype} {sums.shape})")
+    rows = [[int(v) for v in r] for r in sums.tolist()]
+    out = {"n": np.array([r[1] for r in rows], dtype=np.int64), "count": np.array([r[0] for r in rows], dtype=np.int64),
+           "max": np.array([r[4] for r in rows], dtype=np.int64)}
+    out["fraction"] = np.array([r[1] / r[0] if r[0] else math.nan for r in rows], dtype=np.float64)
+    ms = [_mean_std(r[1], r[2], r[3]) for r in rows]
+    out["mean"] = np.array([m for m, _ in ms], dtype=np.float64)
+    out["std"] = np.array([s for _, s in ms], dtype=np.float64)
+    return out
+
+
+def cell_heights(height, pos, build=None):
+    """The per-cell table of a fishnet (city_grid.fishgrid_windows) over a predicted city: heights_from_sums of window_sums(height, pos,
+    build) -- the pixels with height > 0 and, with ``build``, class > 0.  One launch and one device-to-host copy of N x 5 int64.  Raster
+    units (predict_city's height is round(10 h))."""
+    return heights_from_sums(window_sums(height, pos, build).cpu().numpy())
+
+
+def aggregate_city(height, block, build=None):
+    """A coarser product of a predicted city: dict of device (Hb, Wb) rasters over the block x block cells (block 4: 10 m, 40: 100 m,
+    400: 1 km at 2.5 m pixels).  ``n`` (selected pixels), ``count`` (the block's pixels, from geometry) and ``max`` int64; ``mean = sum /
+    n`` (NaN where n == 0), ``fraction = n / count`` and ``density = sum / count`` (the mean over ALL pixels of the block) float64, each
+    one division of exactly converted integers.  Raster units."""
+    s = block_sums(height, block, build)
+    block = int(block)
+    H, W = height.shape
+    ys = torch.arange(s.shape[1], dtype=torch.int64, device=s.device) * block
+    xs = torch.arange(s.shape[2], dtype=torch.int64, device=s.device) * block
+    count = torch.clamp(H - ys, max=block)[:, None] * torch.clamp(W - xs, max=block)[None, :]
+    n, total = s[0], s[1].double()                                       # (sum < 2^47: exact in float64)
+    return {"n": n, "count": count, "max": s[3], "mean": total / n.double(), "fraction": n.double() / count.double(),
+            "density": total / count.double()}
+
+
+def city_summary(height, build=None, bin_width=10, nbins=256, num_class=7):
+    """The whole raster's numbers, as the reference reports them per urban centre: dict of ``count`` (pixels), ``n`` (selected: height
+    > 0 and, with ``build``, class > 0), ``mean``, ``std`` (population), ``max`` -- Python numbers in raster units --, ``hist`` ((nbins,)
+    int64 numpy: value_histogram(height, bin_width, nbins, build)) and ``class_counts`` ((num_class,) int64 numpy, the last class open;
+    None without ``build``).  Block partials are added in int64 on the device; one small result is read back at the end."""
+    s = block_sums(height, 256, build)
+    parts = [s[:3].sum(dim=(1, 2)), s[3].max().reshape(1), value_histogram(height, bin_width, nbins, build)]
+    if build is not None:
+        parts.append(value_histogram(build, 1, num_class, value_threshold=-1))
+    r = [int(v) for v in torch.cat(parts).cpu().tolist()]
+    mean, std = _mean_std(r[0], r[1], r[2])
+    return {"count": int(height.shape[0]) * int(height.shape[1]), "n": r[0], "mean": mean, "std": std, "max": r[3],
+            "hist": np.array(r[4:4 + nbins], dtype=np.int64),
+            "class_counts": None if build is None else np.array(r[4 + nbins:], dtype=np.int64)}
