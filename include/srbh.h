@@ -798,7 +798,11 @@ int srbh_wmse_grad(const float* pred, const float* target, const float* weight, 
 /* srbh_cedice_sums: logits (B,C,HW) fp32 with element strides (b,c,p) -- NCHW and channels_last both work --,
  * labels (B*HW) int64 in [0,C), weight (B*HW) fp32 or NULL.  out4 += [ sum w*CE, sum pb*tb, sum pb, sum tb ] with
  * CE = -log softmax_y (selfloss.py:149,157), pb = softmax[1:].sum (:160-161), tb = (y > 0) (:162).
- * srbh_cedice_grad: dlogits (same strides) = g3[0]*d(sum w*CE) + g3[1]*d(sum pb*tb) + g3[2]*d(sum pb).              */
+ * srbh_cedice_grad: dlogits (same strides) = g3[0]*d(sum w*CE) + g3[1]*d(sum pb*tb) + g3[2]*d(sum pb); elements between
+ * the strided logits are not written.
+ * A label outside [0,C) (the reference raises): srbh_cedice_sums makes out4[0] NaN and counts the pixel in out4[1..3] by
+ * tb = (y > 0) alone; srbh_cedice_grad writes a FINITE gradient there, the softmax with no one-hot class:
+ * dlogits_c = g3[0]*w*s_c + (g3[1]*tb + g3[2])*s_0*(s_c - [c == 0]).  The NaN of the sum is the signal, not the gradient. */
 int srbh_cedice_sums(const float* logits, int B, int C, long HW, long b_stride, long c_stride, long p_stride,
                      const long long* labels, const float* weight, double* out4, void* stream);
 int srbh_cedice_grad(const float* logits, int B, int C, long HW, long b_stride, long c_stride, long p_stride,
