@@ -28,6 +28,7 @@ __all__ = ["fishgrid_windows", "cell_counts", "stats_from_counts", "compare_from
            "city_windows"]
 
 _CELL_TYPES = {torch.uint16: 1, torch.int16: 2, torch.uint8: 3}            # include/srbh.h SRBH_GRID_U16 / _I16 / _U8
+_CELL_WHAT = "uint8, uint16 or int16 (a float's cast to uint8 is not defined outside 0..255)"
 
 
 # ---- the fishnet (generate_WSF_mask_Globeheight_grid.py:275-449) ------------------------------------------------------------------------
@@ -58,22 +59,59 @@ def fishgrid_windows(width, height, window=64, offset=56, unique=False):
 
 
 # ---- the kernel ---------------------------------------------------------------------------------------------------------------------------
-def _raster(name, t):
-    if not (torch.is_tensor(t) and t.dim() == 2):
-        raise ValueError(f"cell_counts: {name} must be an (H, W) tensor (got {getattr(t, 'shape', type(t))})")
-    if not t.is_cuda:
-        raise RuntimeError(f"cell_counts (libsrbh): {name} must be a device tensor -- there is no CPU path")
-    if t.dtype not in _CELL_TYPES:
-        raise TypeError(f"cell_counts: {name} is {t.dtype}; the rasters are uint8, uint16 or int16 (a float's cast to uint8 is not "
-                        "defined outside 0..255)")
-    if min(t.shape) < 1:
-        raise ValueError(f"cell_counts: {name} {tuple(t.shape)} is empty")
-    if t.shape[1] > 1 and t.stride(1) != 1:
-        raise ValueError(f"cell_counts: {name} has stride {t.stride(1)} along W; it must be 1 (a band or a crop is fine, a transpose is not)")
-    t = t.detach()
-    if t.shape[0] > 1 and t.stride(0) < t.shape[1]:                 # (an expanded row: rows that overlap cannot be read in place)
-        t = t.contiguous()
-    return t, max(t.stride(0), t.shape[1])
+# The argument path of every raster entry (here and in city_summary): ``fn`` is the caller's name, ``names`` what it calls its two
+# rasters, ``types`` its dtype table and ``what`` that table in words.  Everything that can be judged without a device is judged first
+# (and is testable without one); the device is asked for last.
+def _check_rasters(fn, names, a, b, types, what):
+    """the checks of one or two rasters (``b`` may be None) that need no device: shapes, types, strides -> (H, W)"""
+    for name, t in list(zip(names, (a, b)))[:1 if b is None else 2]:
+        if not (torch.is_tensor(t) and t.dim() == 2):
+            raise ValueError(f"{fn}: {name} must be an (H, W) tensor (got {getattr(t, 'shape', type(t))})")
+        if t.dtype not in types:
+            raise TypeError(f"{fn}: {name} is {t.dtype}; the rasters are {what}")
+        if min(t.shape) < 1:
+            raise ValueError(f"{fn}: {name} {tuple(t.shape)} is empty")
+        if t.shape[1] > 1 and t.stride(1) != 1:
+            raise ValueError(f"{fn}: {name} has stride {t.stride(1)} along W; it must be 1 (a band or a crop is fine, a transpose is not)")
+    H, W = a.shape
+    if b is not None and (tuple(b.shape) != (H, W) or b.device != a.device):
+        raise ValueError(f"{fn}: {names[1]} {tuple(b.shape)} on {b.device} does not match {names[0]}'s {H} x {W} raster on {a.device}")
+    if H * W >= 2 ** 31:
+        raise ValueError(f"{fn}: a raster of {H} x {W} pixels; counts are formed in 32 bits, so H * W must stay below 2^31")
+    return H, W
+
+
+def _check_windows(fn, pos, W, H, device):
+    """``pos`` judged without a device -> (N, 4) int32 windows, N > 0: the device tensor itself, or the host windows, validated to lie
+    inside the raster, for the caller to upload"""
+    if torch.is_tensor(pos) and pos.is_cuda:
+        if pos.dtype != torch.int32 or pos.dim() != 2 or pos.shape[1] != 4 or pos.device != device:
+            raise ValueError(f"{fn}: a device pos must be an (N, 4) int32 tensor on {device} (got {pos.dtype} {tuple(pos.shape)} on "
+                             f"{pos.device})")
+    else:
+        try:
+            pos = torch.from_numpy(check_windows(pos, W, H, tile=max(W, H)).astype(np.int32))
+        except ValueError as e:
+            raise ValueError(f"{fn}: {e}") from None
+    if pos.shape[0] == 0:
+        raise ValueError(f"{fn}: no windows")
+    return pos
+
+
+def _on_device(fn, names, a, b):
+    """checked rasters -> (a, its row stride, b or None, its row stride), read in place; refuses host tensors"""
+    out = []
+    for name, t in zip(names, (a, b)):
+        if t is None:
+            out += [None, 0]
+            continue
+        if not t.is_cuda:
+            raise RuntimeError(f"{fn} (libsrbh): {name} must be a device tensor -- there is no CPU path")
+        t = t.detach()
+        if t.shape[0] > 1 and t.stride(0) < t.shape[1]:             # (an expanded row: rows that overlap cannot be read in place)
+            t = t.contiguous()
+        out += [t, max(t.stride(0), t.shape[1])]
+    return out
 
 
 def cell_counts(mask, pos, other=None, threshold=0, as_uint8=True):
@@ -83,33 +121,13 @@ def cell_counts(mask, pos, other=None, threshold=0, as_uint8=True):
     raster and uploaded; a device int32 (N, 4) tensor is used as is (the kernel counts only what lies inside the raster).
     ``count`` = the window's pixels inside the raster, ``n_a`` = those with f(mask) > threshold, ``n_b`` the same for ``other``, ``n_and``
     both (0 without ``other``); f = the value's low eight bits (``as_uint8``, the reference's ``.astype(numpy.uint8)``) or the value."""
-    mask, rs_a = _raster("mask", mask)
-    H, W = mask.shape
-    rs_b = 0
-    if other is not None:
-        other, rs_b = _raster("other", other)
-        if tuple(other.shape) != (H, W) or other.device != mask.device:
-            raise ValueError(f"cell_counts: other {tuple(other.shape)} on {other.device} does not match mask's {H} x {W} raster on "
-                             f"{mask.device}")
-    if H * W >= 2 ** 31:
-        raise ValueError(f"cell_counts: a raster of {H} x {W} pixels; a window is counted in 32 bits, so H * W must stay below 2^31")
+    H, W = _check_rasters("cell_counts", ("mask", "other"), mask, other, _CELL_TYPES, _CELL_WHAT)
     threshold = int(threshold)
     if not -32768 <= threshold <= 65535:
         raise ValueError(f"cell_counts: threshold={threshold} outside -32768..65535")
-    if torch.is_tensor(pos) and pos.is_cuda:
-        if pos.dtype != torch.int32 or pos.dim() != 2 or pos.shape[1] != 4 or pos.device != mask.device:
-            raise ValueError(f"cell_counts: a device pos must be an (N, 4) int32 tensor on {mask.device} (got {pos.dtype} "
-                             f"{tuple(pos.shape)} on {pos.device})")
-        pos_dev = pos.contiguous()
-    else:
-        try:
-            p = check_windows(pos, W, H, tile=max(W, H))
-        except ValueError as e:
-            raise ValueError(f"cell_counts: {e}") from None
-        pos_dev = torch.from_numpy(p.astype(np.int32)).to(mask.device)
-    n = pos_dev.shape[0]
-    if n == 0:
-        raise ValueError("cell_counts: no windows")
+    pos = _check_windows("cell_counts", pos, W, H, mask.device)
+    mask, rs_a, other, rs_b = _on_device("cell_counts", ("mask", "other"), mask, other)
+    pos_dev, n = pos.to(mask.device).contiguous(), pos.shape[0]
     out = torch.empty((n, 4), dtype=torch.int64, device=mask.device)
     with torch.cuda.device(mask.device):
         _lib.check(_lib.lib().srbh_cell_counts(mask.data_ptr(), _CELL_TYPES[mask.dtype], rs_a,

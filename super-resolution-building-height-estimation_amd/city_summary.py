@@ -25,8 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .city_grid import _raster
-from .loader_math import check_windows
+from .city_grid import _check_rasters, _check_windows, _on_device
 
 __all__ = ["window_sums", "block_sums", "value_histogram", "heights_from_sums", "cell_heights", "aggregate_city", "city_summary"]
 
@@ -35,44 +34,18 @@ MAX_BINS = 4096
 
 
 # ---- argument handling --------------------------------------------------------------------------------------------------------------------
-# city_grid._raster's checks in another order: everything that can be judged without a device is judged first (and is testable without
-# one); the device is asked for last.
-def _one(fn, name, t):
-    if not (torch.is_tensor(t) and t.dim() == 2):
-        raise ValueError(f"{fn}: {name} must be an (H, W) tensor (got {getattr(t, 'shape', type(t))})")
-    if t.dtype not in _SUM_TYPES:
-        raise TypeError(f"{fn}: {name} is {t.dtype}; the rasters are uint16 or uint8 (int16 and float rasters are out of scope)")
-    if min(t.shape) < 1:
-        raise ValueError(f"{fn}: {name} {tuple(t.shape)} is empty")
-    if t.shape[1] > 1 and t.stride(1) != 1:
-        raise ValueError(f"{fn}: {name} has stride {t.stride(1)} along W; it must be 1 (a band or a crop is fine, a transpose is not)")
+# city_grid's argument path: everything that can be judged without a device is judged first (and is testable without one); the device is
+# asked for last.
+_NAMES = ("value", "mask")
 
 
 def _rasters(fn, value, mask, value_threshold, mask_threshold):
     """the checks that need no device: shapes, types, strides, thresholds -> (H, W, vthr, mthr)"""
-    _one(fn, "value", value)
-    H, W = value.shape
-    if mask is not None:
-        _one(fn, "mask", mask)
-        if tuple(mask.shape) != (H, W) or mask.device != value.device:
-            raise ValueError(f"{fn}: mask {tuple(mask.shape)} on {mask.device} does not match value's {H} x {W} raster on {value.device}")
-    if H * W >= 2 ** 31:
-        raise ValueError(f"{fn}: a raster of {H} x {W} pixels; counts are formed in 32 bits, so H * W must stay below 2^31")
+    H, W = _check_rasters(fn, _NAMES, value, mask, _SUM_TYPES, "uint16 or uint8 (int16 and float rasters are out of scope)")
     vthr, mthr = int(value_threshold), int(mask_threshold)
     if not (-1 <= vthr <= 65535 and -1 <= mthr <= 65535):
         raise ValueError(f"{fn}: a threshold ({vthr}, {mthr}) outside -1..65535")
     return H, W, vthr, mthr
-
-
-def _on_device(fn, value, mask):
-    """-> (value, its row stride, mask or None, its row stride), read in place; refuses host tensors"""
-    for name, t in (("value", value), ("mask", mask)):
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f"{fn} (libsrbh): {name} must be a device tensor -- there is no CPU path")
-    value, rs_v = _raster("value", value)                                # (types and strides are checked: this only resolves the row stride)
-    if mask is None:
-        return value, rs_v, None, 0
-    return (value, rs_v) + _raster("mask", mask)
 
 
 def _abi(value, rs_v, mask, rs_m, H, W):
@@ -89,22 +62,9 @@ def window_sums(value, pos, mask=None, value_threshold=0, mask_threshold=0):
     as is (the kernel sums only what lies inside the raster).  ``count`` = the window's pixels inside the raster, ``n`` = the selected
     ones, ``sum`` / ``sumsq`` / ``max`` over the selected pixels in raster units (0 when n == 0)."""
     H, W, vthr, mthr = _rasters("window_sums", value, mask, value_threshold, mask_threshold)
-    dev_pos = torch.is_tensor(pos) and pos.is_cuda
-    if dev_pos:
-        if pos.dtype != torch.int32 or pos.dim() != 2 or pos.shape[1] != 4 or pos.device != value.device:
-            raise ValueError(f"window_sums: a device pos must be an (N, 4) int32 tensor on {value.device} (got {pos.dtype} "
-                             f"{tuple(pos.shape)} on {pos.device})")
-        n = pos.shape[0]
-    else:
-        try:
-            p = check_windows(pos, W, H, tile=max(W, H))
-        except ValueError as e:
-            raise ValueError(f"window_sums: {e}") from None
-        n = p.shape[0]
-    if n == 0:
-        raise ValueError("window_sums: no windows")
-    value, rs_v, mask, rs_m = _on_device("window_sums", value, mask)
-    pos_dev = pos.contiguous() if dev_pos else torch.from_numpy(p.astype(np.int32)).to(value.device)
+    pos = _check_windows("window_sums", pos, W, H, value.device)
+    value, rs_v, mask, rs_m = _on_device("window_sums", _NAMES, value, mask)
+    pos_dev, n = pos.to(value.device).contiguous(), pos.shape[0]
     out = torch.empty((n, 5), dtype=torch.int64, device=value.device)
     with torch.cuda.device(value.device):
         _lib.check(_lib.lib().srbh_window_sums(*_abi(value, rs_v, mask, rs_m, H, W), pos_dev.data_ptr(), n, vthr, mthr, out.data_ptr(),
@@ -118,7 +78,7 @@ def block_sums(value, block, mask=None, value_threshold=0, mask_threshold=0):
     Raster units."""
     H, W, vthr, mthr = _rasters("block_sums", value, mask, value_threshold, mask_threshold)
     block = _block("block_sums", block)
-    value, rs_v, mask, rs_m = _on_device("block_sums", value, mask)
+    value, rs_v, mask, rs_m = _on_device("block_sums", _NAMES, value, mask)
     out = torch.empty((4, -(-H // block), -(-W // block)), dtype=torch.int64, device=value.device)
     with torch.cuda.device(value.device):
         _lib.check(_lib.lib().srbh_block_sums(*_abi(value, rs_v, mask, rs_m, H, W), min(block, 2 ** 31 - 1), vthr, mthr, out.data_ptr(),
@@ -142,7 +102,7 @@ def value_histogram(value, bin_width=1, nbins=256, mask=None, value_threshold=0,
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= hi:
             raise ValueError(f"value_histogram: {name}={v!r} outside 1..{hi}")
     bin_width, nbins = int(bin_width), int(nbins)
-    value, rs_v, mask, rs_m = _on_device("value_histogram", value, mask)
+    value, rs_v, mask, rs_m = _on_device("value_histogram", _NAMES, value, mask)
     need = _lib.lib().srbh_value_hist_ws_bytes(H, W, nbins)
     if workspace is None:
         workspace = torch.empty(need, dtype=torch.uint8, device=value.device)

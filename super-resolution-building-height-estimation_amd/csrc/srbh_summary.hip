@@ -6,14 +6,8 @@
 // A pixel is SELECTED when it lies inside the raster, v > vthr and (no mask or m > mthr).  v and m are uint16 or uint8 rasters, each read
 // in place through its own row stride.  Everything is an integer: exact, no order, bit-equal between runs.  No floating point.
 //
-// One walk serves the three entries.  A rectangle [x0, x1) x [y0, y0 + rows) inside the raster is cut, row by row, into groups of
-// P = 16 / sizeof(element of v) pixels that start on 16-byte boundaries of v's ADDRESS (the alignment is taken per row: an odd W, a
-// cropped view and xoff = k * 56 give every row its own); a TEAM of lanes takes the (row, group) pairs in turn.  As in srbh_cells.hip:
-//   * a group whose P pixels all lie inside the raster's row [0, W) is fetched by one aligned 16-byte load, and the pixels outside
-//     [x0, x1) are masked off -- the head and the tail of a rectangle's row read raster pixels next to it, never anything else;
-//   * any other group is fetched pixel by pixel, each load predicated on the rectangle, which lies inside the raster.
-// The same P pixels of m are fetched by the same rule with a load of element alignment (m has its own element size, stride and
-// alignment).  So no load touches a byte outside the rows' own bytes of either raster, whatever pos holds.
+// One walk serves the three entries (srbh_raster_walk.h: the walk in 16-byte groups of v's address by a TEAM of lanes, and why no load
+// leaves a raster whatever pos holds):
 //
 //   srbh_window_sums   TEAM = one workgroup of 256 lanes per window (windows overlap and have any size): {count, n, sum, sumsq, max}.
 //   srbh_block_sums    every block x block cell of the raster has ONE owner, so nothing is added across owners and the raster is read
@@ -27,16 +21,13 @@
 // Overflow.  A group holds at most 16 values below 2^16: its sum stays below 2^20 and is formed in 32 bits; everything a lane keeps
 // across groups is 64-bit.  v * v reaches (2^16 - 1)^2 < 2^32: the product is a 32 x 32 -> 64-bit multiply-add (one v_mad_u64_u32), so
 // the sum of squares is 64-bit from the first add; H * W < 2^31 keeps it below 2^31 * 2^32 = 2^63.  Counts: int32, below H * W.
-#include "srbh_internal.h"
+#include "srbh_raster_walk.h"
 
 namespace {
 using namespace srbh;
 
 struct SumParams {
-    const unsigned char* v;
-    const unsigned char* m;         // NULL: no mask
-    long rsV, rsM;                  // row strides in elements
-    int H, W;
+    Rasters r;                      // a: the values v, b: the mask m
     int vthr, mthr;
 };
 
@@ -44,138 +35,66 @@ struct Acc {
     int n;
     unsigned mx;
     unsigned long long sum, sq;
+    __device__ __forceinline__ Acc down(int o) const { return {__shfl_down(n, o, 64), __shfl_down(mx, o, 64), __shfl_down(sum, o, 64), __shfl_down(sq, o, 64)}; }
+    __device__ __forceinline__ void merge(const Acc& o) {
+        n += o.n;
+        sum += o.sum;
+        sq += o.sq;
+        mx = mx > o.mx ? mx : o.mx;
+    }
 };
 
-// val[j] = pixel c0 + j of the row at `row` (its pixel 0) for every j of [lo, hi), a non-empty part of [0, P) whose pixels lie inside
-// [0, W); the other entries hold raster pixels of the same row or 0.  ALIGNED: row + c0 * E is a 16-byte boundary whenever the wide
-// load is taken (P * E == 16).
-template <int E, int P, bool ALIGNED>
-__device__ __forceinline__ void group_vals(const unsigned char* row, int c0, int W, int lo, int hi, unsigned* val) {
-    constexpr int WORDS = P * E / 4;
-    if (c0 >= 0 && c0 <= W - P) {
-        unsigned w[WORDS];
-        const unsigned char* src = row + (long)c0 * E;
-        if (ALIGNED) {
-            const uint4 q = *reinterpret_cast<const uint4*>(src);
-            w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
-        } else {
-            __builtin_memcpy(w, __builtin_assume_aligned(src, E), sizeof w);
-        }
+// The selection rule on one group: wv = the words of its P values of v, and bit j of the result: pixel j of the group is selected.  The
+// value group is thresholded before the mask group is loaded.
+template <int EV, int EM>
+__device__ __forceinline__ unsigned select_group(const SumParams& p, const Group<EV, EM>& g, unsigned* wv) {
+    using G = Group<EV, EM>;
+    g.load_a(wv);
+    unsigned sel = 0;
 #pragma unroll
-        for (int j = 0; j < P; ++j) val[j] = E == 1 ? (w[j >> 2] >> (8 * (j & 3))) & 0xffu : (w[j >> 1] >> (16 * (j & 1))) & 0xffffu;
-    } else {
+    for (int j = 0; j < G::P; ++j) sel |= ((int)group_pixel<EV>(wv, j) > p.vthr ? 1u : 0u) << j;
+    sel &= g.inside();
+    if (EM) {
+        unsigned wm[G::WORDS_B];
+        g.load_b(wm);
+        unsigned ms = 0;
 #pragma unroll
-        for (int j = 0; j < P; ++j) {
-            val[j] = 0u;
-            if (j >= lo && j < hi) val[j] = E == 1 ? (unsigned)row[c0 + j] : (unsigned)reinterpret_cast<const unsigned short*>(row)[c0 + j];
-        }
+        for (int j = 0; j < G::P; ++j) ms |= ((int)group_pixel<G::EBB>(wm, j) > p.mthr ? 1u : 0u) << j;
+        sel &= ms;
     }
+    return sel;
 }
 
-// The rectangle [x0, x1) x [y0, y0 + rows) -- inside the raster, not empty -- walked by `team` lanes, this one being lane `tid` of them:
-// f(val, sel) once per (row, group) of this lane, val the P values of v, bit j of sel: pixel j of the group is selected.
-template <int EV, int EM, class F>
-__device__ __forceinline__ void walk(const SumParams& p, int x0, int x1, int y0, int rows, int tid, int team, F&& f) {
-    constexpr int P = 16 / EV;
-    // a row's groups: group k holds the pixels x0 - mis + k * P .. + P - 1, mis < P the pixels between the 16-byte boundary below the
-    // row's first pixel and that pixel; at most cpr groups reach into [x0, x1)
-    const int cpr = (int)(((long)(x1 - x0) + 2 * P - 2) / P);
-    const int drow = team / cpr, dk = team - drow * cpr;             // (32-bit index divisions: team <= 2048 * 256)
-    long row = tid / cpr;
-    int k = tid - (int)row * cpr;
-    while (row < rows) {
-        const long y = y0 + row;
-        const unsigned char* rowV = p.v + y * p.rsV * EV;
-        const int mis = (int)(((uintptr_t)rowV + (uintptr_t)x0 * EV) & 15u) / EV;
-        const long c0l = (long)x0 - mis + (long)k * P;
-        if (c0l < x1) {
-            const int c0 = (int)c0l;
-            const int lo = x0 > c0 ? x0 - c0 : 0, hi = x1 - c0 < P ? x1 - c0 : P;      // the rectangle's pixels of this group: hi > lo
-            unsigned val[P];
-            group_vals<EV, P, true>(rowV, c0, p.W, lo, hi, val);
-            unsigned sel = 0;
+// the selected pixels of the rectangle [x0, x1) x [y0, y0 + rows) that lane `tid` of `team` walks, added to a
+template <int EV, int EM>
+__device__ __forceinline__ void sum_rect(const SumParams& p, int x0, int x1, int y0, int rows, int tid, int team, Acc& a) {
+    using G = Group<EV, EM>;
+    walk_rect<EV, EM>(p.r, x0, x1, y0, rows, tid, team, [&](const G& g) {
+        unsigned wv[G::WORDS_A];
+        const unsigned sel = select_group(p, g, wv);
+        unsigned s32 = 0;                                             // at most 16 values below 2^16
 #pragma unroll
-            for (int j = 0; j < P; ++j) sel |= ((int)val[j] > p.vthr ? 1u : 0u) << j;
-            sel &= ((1u << (hi - lo)) - 1u) << lo;
-            if (EM) {
-                constexpr int EMM = EM ? EM : 1;
-                unsigned mv[P];
-                group_vals<EMM, P, false>(p.m + y * p.rsM * EMM, c0, p.W, lo, hi, mv);
-                unsigned ms = 0;
-#pragma unroll
-                for (int j = 0; j < P; ++j) ms |= ((int)mv[j] > p.mthr ? 1u : 0u) << j;
-                sel &= ms;
-            }
-            f(val, sel);
+        for (int j = 0; j < G::P; ++j) {
+            const unsigned s = (sel >> j) & 1u ? group_pixel<EV>(wv, j) : 0u;
+            s32 += s;
+            a.sq += (unsigned long long)s * s;                        // 32 x 32 -> 64
+            a.mx = a.mx > s ? a.mx : s;
         }
-        row += drow;
-        k += dk;
-        if (k >= cpr) { k -= cpr; ++row; }
-    }
-}
-
-template <int P>
-__device__ __forceinline__ void add_group(Acc& a, const unsigned* val, unsigned sel) {
-    unsigned s32 = 0;                                                 // at most 16 values below 2^16
-#pragma unroll
-    for (int j = 0; j < P; ++j) {
-        const unsigned s = (sel >> j) & 1u ? val[j] : 0u;
-        s32 += s;
-        a.sq += (unsigned long long)s * s;                            // 32 x 32 -> 64
-        a.mx = a.mx > s ? a.mx : s;
-    }
-    a.n += __popc(sel);
-    a.sum += s32;
-}
-
-// the team's lanes folded into its lane 0.  TEAM: 1 (a lane), 64 (a wave), 256 (the workgroup; every lane of it calls)
-template <int TEAM>
-__device__ __forceinline__ void fold(Acc& a) {
-    if (TEAM == 1) return;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        a.n += __shfl_down(a.n, o, 64);
-        a.sum += __shfl_down(a.sum, o, 64);
-        a.sq += __shfl_down(a.sq, o, 64);
-        const unsigned other = __shfl_down(a.mx, o, 64);
-        a.mx = a.mx > other ? a.mx : other;
-    }
-    if (TEAM == 256) {
-        __shared__ unsigned long long red[2][4];
-        __shared__ int red_n[4];
-        __shared__ unsigned red_mx[4];
-        const int t = threadIdx.x, wave = t >> 6;
-        if ((t & 63) == 0) { red[0][wave] = a.sum; red[1][wave] = a.sq; red_n[wave] = a.n; red_mx[wave] = a.mx; }
-        __syncthreads();
-        if (t == 0) {
-            a.sum = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-            a.sq = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
-            a.n = ((red_n[0] + red_n[1]) + red_n[2]) + red_n[3];
-#pragma unroll
-            for (int w = 1; w < 4; ++w) a.mx = a.mx > red_mx[w] ? a.mx : red_mx[w];
-        }
-    }
+        a.n += __popc(sel);
+        a.sum += s32;
+    });
 }
 
 // EV, EM: element sizes of v and m in bytes (EM == 0: no mask)
 template <int EV, int EM>
 __global__ __launch_bounds__(256) void window_sums_kernel(const SumParams p, const int* __restrict__ pos, long long* __restrict__ out) {
-    const int* q = pos + 4 * (long)blockIdx.x;
-    const int xoff = q[0], yoff = q[1], xcount = q[2], ycount = q[3];
-    // the window clipped to the raster, in 64 bits so that no content of pos overflows
-    const long long X0 = xoff > 0 ? xoff : 0, Y0 = yoff > 0 ? yoff : 0;
-    long long X1 = (long long)xoff + xcount, Y1 = (long long)yoff + ycount;
-    X1 = X1 < p.W ? X1 : p.W;
-    Y1 = Y1 < p.H ? Y1 : p.H;
-    const bool any = xcount > 0 && ycount > 0 && X1 > X0 && Y1 > Y0;
-    const int x0 = any ? (int)X0 : 0, x1 = any ? (int)X1 : 0, y0 = any ? (int)Y0 : 0, rows = any ? (int)(Y1 - Y0) : 0;
+    const Rect w = clip_window(pos + 4 * (long)blockIdx.x, p.r.H, p.r.W);
     Acc a = {0, 0u, 0ull, 0ull};
-    if (any)                                                          // uniform
-        walk<EV, EM>(p, x0, x1, y0, rows, threadIdx.x, 256, [&](const unsigned* val, unsigned sel) { add_group<16 / EV>(a, val, sel); });
-    fold<256>(a);
+    if (w.any) sum_rect<EV, EM>(p, w.x0, w.x1, w.y0, w.rows, threadIdx.x, 256, a);      // uniform
+    fold_team<256>(a);
     if (threadIdx.x == 0) {
         long long* o = out + 5 * (long)blockIdx.x;
-        o[0] = (long long)(x1 - x0) * rows;
+        o[0] = (long long)(w.x1 - w.x0) * w.rows;
         o[1] = a.n;
         o[2] = (long long)a.sum;
         o[3] = (long long)a.sq;
@@ -195,10 +114,10 @@ __global__ __launch_bounds__(256) void block_sums_kernel(const SumParams p, int 
         const int by = (int)((unsigned)b / (unsigned)Wb), bx = (int)b - by * Wb;      // b < Hb * Wb < 2^31
         const int x0 = bx * block, y0 = by * block;                  // below W and H
         const long long X1 = (long long)x0 + block, Y1 = (long long)y0 + block;
-        const int x1 = X1 < p.W ? (int)X1 : p.W, y1 = Y1 < p.H ? (int)Y1 : p.H;
-        walk<EV, EM>(p, x0, x1, y0, y1 - y0, tid, TEAM, [&](const unsigned* val, unsigned sel) { add_group<16 / EV>(a, val, sel); });
+        const int x1 = X1 < p.r.W ? (int)X1 : p.r.W, y1 = Y1 < p.r.H ? (int)Y1 : p.r.H;
+        sum_rect<EV, EM>(p, x0, x1, y0, y1 - y0, tid, TEAM, a);
     }
-    fold<TEAM>(a);
+    fold_team<TEAM>(a);
     if (b < nb && tid == 0) {
         out[b] = a.n;
         out[nb + b] = (long long)a.sum;
@@ -229,11 +148,13 @@ __global__ __launch_bounds__(256) void value_hist_kernel(const SumParams p, unsi
     for (int i = t; i < nbins; i += 256) hist[i] = 0u;
     __syncthreads();
     const unsigned last = (unsigned)nbins - 1u;
-    walk<EV, EM>(p, 0, p.W, 0, p.H, (int)blockIdx.x * 256 + t, (int)gridDim.x * 256, [&](const unsigned* val, unsigned sel) {
+    walk_rect<EV, EM>(p.r, 0, p.r.W, 0, p.r.H, (int)blockIdx.x * 256 + t, (int)gridDim.x * 256, [&](const Group<EV, EM>& g) {
+        unsigned wv[Group<EV, EM>::WORDS_A];
+        const unsigned sel = select_group(p, g, wv);
 #pragma unroll
         for (int j = 0; j < 16 / EV; ++j) {
             if ((sel >> j) & 1u) {
-                const unsigned qv = magic ? __umulhi(val[j], magic) : val[j];
+                const unsigned v = group_pixel<EV>(wv, j), qv = magic ? __umulhi(v, magic) : v;
                 atomicAdd(&hist[qv < last ? qv : last], 1u);
             }
         }
@@ -264,42 +185,17 @@ __global__ __launch_bounds__(256) void value_hist_fold_kernel(const unsigned* __
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------------
 inline bool sum_type_ok(int type) { return type == SRBH_GRID_U16 || type == SRBH_GRID_U8; }
-inline int sum_esz(int type) { return type == SRBH_GRID_U8 ? 1 : 2; }
 
 // the checks common to the three entries; fills p.  SRBH_OK or SRBH_ERR_ARG (the error text is set)
 int sum_params(const char* who, const void* v, int typeV, long rsV, const void* m, int typeM, long rsM, int H, int W, int vthr, int mthr,
                SumParams* p) {
-    SRBH_REQUIRE(v, "%s: null value raster", who);
     SRBH_REQUIRE(sum_type_ok(typeV) && (!m || sum_type_ok(typeM)),
                  "%s: element type typeV=%d typeM=%d; the rasters are uint16 (1) or uint8 (3) -- int16, float32 and unknown codes are refused",
                  who, typeV, typeM);
-    SRBH_REQUIRE(H > 0 && W > 0, "%s: bad geometry H=%d W=%d", who, H, W);
-    SRBH_REQUIRE(rsV >= W && (!m || rsM >= W), "%s: a row stride (%ld, %ld) is below W=%d", who, rsV, m ? rsM : rsV, W);
-    SRBH_REQUIRE((long)H * W < 0x80000000L, "%s: H * W = %ld must stay below 2^31", who, (long)H * W);
     SRBH_REQUIRE(vthr >= -1 && vthr <= 65535 && mthr >= -1 && mthr <= 65535, "%s: a threshold (vthr=%d, mthr=%d) outside -1..65535", who,
                  vthr, mthr);
-    const int ev = sum_esz(typeV), em = m ? sum_esz(typeM) : 0;
-    SRBH_REQUIRE((uintptr_t)v % ev == 0 && (!m || (uintptr_t)m % em == 0), "%s: a raster is not aligned to its element size", who);
-    p->v = (const unsigned char*)v; p->m = (const unsigned char*)m;
-    p->rsV = rsV; p->rsM = m ? rsM : 0;
-    p->H = H; p->W = W; p->vthr = vthr; p->mthr = mthr;
-    return SRBH_OK;
-}
-
-// f(integral_constant EV, integral_constant EM) for the element sizes of p's rasters
-template <class F>
-inline void with_sizes(int typeV, const void* m, int typeM, F&& f) {
-    using std::integral_constant;
-    const int ev = sum_esz(typeV), em = m ? sum_esz(typeM) : 0;
-    if (ev == 1) {
-        if (em == 0) f(integral_constant<int, 1>{}, integral_constant<int, 0>{});
-        else if (em == 1) f(integral_constant<int, 1>{}, integral_constant<int, 1>{});
-        else f(integral_constant<int, 1>{}, integral_constant<int, 2>{});
-    } else {
-        if (em == 0) f(integral_constant<int, 2>{}, integral_constant<int, 0>{});
-        else if (em == 1) f(integral_constant<int, 2>{}, integral_constant<int, 1>{});
-        else f(integral_constant<int, 2>{}, integral_constant<int, 2>{});
-    }
+    p->vthr = vthr; p->mthr = mthr;
+    return rasters_checked(who, v, typeV, rsV, m, typeM, rsM, H, W, &p->r);
 }
 
 }  // namespace
