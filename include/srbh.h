@@ -720,6 +720,16 @@ int srbh_pwconv_bwd_data(const float* dy, const float* w, float* dx, int B, int 
 int srbh_pwconv_bwd_data_res(const float* dy, const float* w, const float* res, float* dx, int B, int Cin, int Cout, int HW, void* stream);
 size_t srbh_pwconv_bwd_weight_ws_floats(int B, int Cin, int Cout, int HW);
 int srbh_pwconv_bwd_weight(const float* x, const float* dy, float* dw, float* ws, int B, int Cin, int Cout, int HW, void* stream);
+/* Which kernel form the entry points above launch for a shape: host-only queries of the launchers' own rule, nothing is launched (tests
+ * assert the form they mean to run, and that every form the production batches select is one they compare with a reference).
+ * srbh_pwconv_gemm_plan: the forward (M = Cout, K = Cin; srbh_pwconv_fwd / _fwd_wt / _fwd_epi) and the data gradient (M = Cin, K = Cout;
+ * srbh_pwconv_bwd_data / _bwd_data_res).  *family = 0 pw_gemm_kernel | 1 pw_gemm_lds_kernel; *form = the tile 0 16x16 | 1 16x32 | 2 32x32 of
+ * family 0, or the LDS form 1 64x64 | 2 64x128 | 4 32x128; *kw = waves sharing one tile's K (1 | 4 | 16; 1 for every LDS form).
+ * srbh_pwconv_wgrad_plan: *vec = 1 (2x2 planes, one K step per image) | 4 (float4 runs), *kw = waves per 16x16 tile (4 | 16), *nsplit =
+ * image splits (1 ... 64; > 1 needs the workspace and runs the ordered reduce).  SRBH_OK, or an error (nothing stored) for a null pointer,
+ * a dimension <= 0 or, for the weight gradient, a plane that is neither 4 nor a multiple of 16 elements. */
+int srbh_pwconv_gemm_plan(int B, int M, int K, int HW, int* family, int* form, int* kw);
+int srbh_pwconv_wgrad_plan(int B, int Cin, int Cout, int HW, int* vec, int* kw, int* nsplit);
 
 /* ---- inference epilogue: quantise + integer mosaic (predict_realesanet_feature_globe.py:172-204) ------------------
  * accumulate: height [B][th][tw] fp32 (model output, C=1), build logits NHWC [B][th][tw][C] fp32, pos [B][4] int32

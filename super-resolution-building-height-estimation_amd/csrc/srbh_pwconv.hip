@@ -279,10 +279,11 @@ int pick_kw(long tiles, int K) {                  // waves per tile: split K ins
     if (tiles * 4 >= WAVES_WANTED || rounds <= 8) return 4;
     return 16;
 }
-struct WgradPlan { int KW, S; };
+struct WgradPlan { int VEC, KW, S; };      // VEC 1: 2x2 planes, 4: float4 runs
 WgradPlan wgrad_plan(int M, int N, int B, int HW) {
     const long tiles = (long)((M + 15) / 16) * ((N + 15) / 16);
     WgradPlan p;
+    p.VEC = HW == 4 ? 1 : 4;
     p.KW = (tiles >= 1024 || B < 16) ? 4 : 16;
     long S = (3 * WAVES_WANTED + tiles * p.KW - 1) / (tiles * p.KW);    // (~4 waves per SIMD: the K walk is a chain of scattered plane reads)
     const long slots = HW == 4 ? B : (long)B * (HW >> 4);            // K slots a slice strides over (images, or float4 runs)
@@ -322,32 +323,45 @@ int gemm_launch_epi_kw(int kw, const float* W, const float* In, float* Out, int 
 
 #include "srbh_pwgemm_lds_kernel.h"      // the LDS-tiled form for wide products (the tiled prediction's batches)
 
+// the one selection rule of the forward / data-gradient products: the LDS form where its plan takes the product, else the largest
+// pw_gemm_kernel tile whose grid fills the chip and, for 16x16 tiles, the K split (srbh_pwconv_gemm_plan reports exactly this)
+struct GemmPlan {
+    PwLdsPlan lds;          // lds.form != 0: pw_gemm_lds_kernel
+    int tile, kw;           // else pw_gemm_kernel: 0 16x16 | 1 16x32 | 2 32x32, and the waves sharing a tile's K (1 | 4 | 16)
+    int tm, tn;
+    long ncols;
+};
+GemmPlan gemm_plan(int M, int K, int HW, int B) {
+    GemmPlan g{};
+    g.ncols = (long)B * HW;
+    g.kw = 1;
+    g.lds = pw_lds_plan(M, K, HW, g.ncols);
+    if (g.lds.form) return g;
+    const long m16 = (M + 15) / 16, n16 = (g.ncols + 15) / 16;
+    g.tile = pick_tile(m16, n16);
+    const int MI = g.tile == 2 ? 2 : 1, NI = g.tile >= 1 ? 2 : 1;
+    g.tm = (int)((m16 + MI - 1) / MI);
+    g.tn = (int)((n16 + NI - 1) / NI);
+    if (g.tile == 0) g.kw = pick_kw((long)g.tm * g.tn, K);
+    return g;
+}
+
 template <int TRANS_A>
 int gemm_launch_epi(const float* W, const float* In, float* Out, int M, int K, int HW, int B, const PwEpi& ep, hipStream_t st) {
-    const long ncols = (long)B * HW, m16 = (M + 15) / 16, n16 = (ncols + 15) / 16;
-    const PwLdsPlan lp = pw_lds_plan(M, K, HW, ncols);
-    if (lp.form) return pw_lds_launch<TRANS_A, 1>(lp, W, In, Out, M, K, HW, ncols, ep, st);
-    const int t = pick_tile(m16, n16);
-    const int MI = t == 2 ? 2 : 1, NI = t >= 1 ? 2 : 1;
-    const int tm = (int)((m16 + MI - 1) / MI), tn = (int)((n16 + NI - 1) / NI);
-    const int kw = t == 0 ? pick_kw((long)tm * tn, K) : 1;
-    if (t == 2) return gemm_launch_epi_kw<2, 2, TRANS_A>(1, W, In, Out, M, K, HW, ncols, tm, tn, ep, st);
-    if (t == 1) return gemm_launch_epi_kw<1, 2, TRANS_A>(1, W, In, Out, M, K, HW, ncols, tm, tn, ep, st);
-    return gemm_launch_epi_kw<1, 1, TRANS_A>(kw, W, In, Out, M, K, HW, ncols, tm, tn, ep, st);
+    const GemmPlan g = gemm_plan(M, K, HW, B);
+    if (g.lds.form) return pw_lds_launch<TRANS_A, 1>(g.lds, W, In, Out, M, K, HW, g.ncols, ep, st);
+    if (g.tile == 2) return gemm_launch_epi_kw<2, 2, TRANS_A>(1, W, In, Out, M, K, HW, g.ncols, g.tm, g.tn, ep, st);
+    if (g.tile == 1) return gemm_launch_epi_kw<1, 2, TRANS_A>(1, W, In, Out, M, K, HW, g.ncols, g.tm, g.tn, ep, st);
+    return gemm_launch_epi_kw<1, 1, TRANS_A>(g.kw, W, In, Out, M, K, HW, g.ncols, g.tm, g.tn, ep, st);
 }
 
 template <int TRANS_A>
 int gemm_launch(const float* W, const float* In, float* Out, int M, int K, int HW, int B, hipStream_t st) {
-    const long ncols = (long)B * HW, m16 = (M + 15) / 16, n16 = (ncols + 15) / 16;
-    const PwLdsPlan lp = pw_lds_plan(M, K, HW, ncols);
-    if (lp.form) return pw_lds_launch<TRANS_A, 0>(lp, W, In, Out, M, K, HW, ncols, PwEpi{}, st);
-    const int t = pick_tile(m16, n16);
-    const int MI = t == 2 ? 2 : 1, NI = t >= 1 ? 2 : 1;
-    const int tm = (int)((m16 + MI - 1) / MI), tn = (int)((n16 + NI - 1) / NI);
-    const int kw = t == 0 ? pick_kw((long)tm * tn, K) : 1;
-    if (t == 2) return gemm_launch_kw<2, 2, TRANS_A>(1, W, In, Out, M, K, HW, ncols, tm, tn, st);
-    if (t == 1) return gemm_launch_kw<1, 2, TRANS_A>(1, W, In, Out, M, K, HW, ncols, tm, tn, st);
-    return gemm_launch_kw<1, 1, TRANS_A>(kw, W, In, Out, M, K, HW, ncols, tm, tn, st);
+    const GemmPlan g = gemm_plan(M, K, HW, B);
+    if (g.lds.form) return pw_lds_launch<TRANS_A, 0>(g.lds, W, In, Out, M, K, HW, g.ncols, PwEpi{}, st);
+    if (g.tile == 2) return gemm_launch_kw<2, 2, TRANS_A>(1, W, In, Out, M, K, HW, g.ncols, g.tm, g.tn, st);
+    if (g.tile == 1) return gemm_launch_kw<1, 2, TRANS_A>(1, W, In, Out, M, K, HW, g.ncols, g.tm, g.tn, st);
+    return gemm_launch_kw<1, 1, TRANS_A>(g.kw, W, In, Out, M, K, HW, g.ncols, g.tm, g.tn, st);
 }
 }  // namespace
 
@@ -412,7 +426,7 @@ extern "C" int srbh_pwconv_bwd_weight(const float* x, const float* dy, float* dw
     const dim3 grid((unsigned)(tm * tn), p.S);
     hipStream_t st = (hipStream_t)stream;
 #define SRBH_WG(V_, K_) hipLaunchKernelGGL((pw_wgrad_kernel<V_, K_>), grid, dim3(64 * K_), K_ * 4 * 64 * 4, st, dy, x, out, Cout, Cin, HW, B, p.S, tn)
-    if (HW == 4) {
+    if (p.VEC == 1) {
         if (p.KW == 16) SRBH_WG(1, 16);
         else SRBH_WG(1, 4);
     } else {
@@ -425,6 +439,31 @@ extern "C" int srbh_pwconv_bwd_weight(const float* x, const float* dy, float* dw
         hipLaunchKernelGGL(pw_wgrad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ws, dw, n, p.S);
     }
     SRBH_HIP(hipGetLastError());
+    return SRBH_OK;
+}
+
+/* which kernel form the products above run for a shape (host only, launches nothing): the launchers' own rule.
+ * srbh_pwconv_gemm_plan: forward (M = Cout, K = Cin) and data gradient (M = Cin, K = Cout); *family 0 pw_gemm_kernel | 1 pw_gemm_lds_kernel,
+ * *form = tile 0 16x16 | 1 16x32 | 2 32x32, or the LDS form 1 64x64 | 2 64x128 | 4 32x128, *kw = waves sharing a tile's K.
+ * srbh_pwconv_wgrad_plan: *vec 1 (2x2 planes) | 4 (float4 runs), *kw = waves per tile, *nsplit = image splits (> 1: workspace + reduce). */
+extern "C" int srbh_pwconv_gemm_plan(int B, int M, int K, int HW, int* family, int* form, int* kw) {
+    SRBH_REQUIRE(family && form && kw, "srbh_pwconv_gemm_plan: null pointer");
+    SRBH_REQUIRE(B > 0 && M > 0 && K > 0 && HW > 0, "srbh_pwconv_gemm_plan: bad shape");
+    const GemmPlan g = gemm_plan(M, K, HW, B);
+    *family = g.lds.form ? 1 : 0;
+    *form = g.lds.form ? g.lds.form : g.tile;
+    *kw = g.kw;
+    return SRBH_OK;
+}
+
+extern "C" int srbh_pwconv_wgrad_plan(int B, int Cin, int Cout, int HW, int* vec, int* kw, int* nsplit) {
+    SRBH_REQUIRE(vec && kw && nsplit, "srbh_pwconv_wgrad_plan: null pointer");
+    SRBH_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && HW > 0, "srbh_pwconv_wgrad_plan: bad shape");
+    SRBH_REQUIRE(HW == 4 || (HW & 15) == 0, "srbh_pwconv_wgrad_plan: planes of 4 or a multiple of 16 elements (HW = %d)", HW);
+    const WgradPlan p = wgrad_plan(Cout, Cin, B, HW);
+    *vec = p.VEC;
+    *kw = p.KW;
+    *nsplit = p.S;
     return SRBH_OK;
 }
 
