@@ -978,6 +978,58 @@ size_t srbh_value_hist_ws_bytes(int H, int W, int nbins);
 int srbh_value_hist(const void* v, int typeV, long row_strideV, const void* m, int typeM, long row_strideM, int H, int W,
                     int vthr, int mthr, int bin_width, int nbins, long long* hist, void* ws, void* stream);
 
+/* ---- Polygon zones over a city's rasters: the reference's "mean and std of building height in each urban center" (zonal_stats,
+ * demo_preprocess_height_v2.py:450-570: one gdal.RasterizeLayer, one window read and one numpy.ma sum per feature there; every zone in
+ * one call here, rasterised on the device with no zone raster ever stored; csrc/srbh_zones.hip) -------------------------------------------
+ * v, m, the row strides, vthr and mthr: as for srbh_window_sums above.  A pixel is SELECTED when it is selected there AND lies in the zone.
+ *
+ * The zone rule (this project's own statement, modelled on RasterizeLayer without ALL_TOUCHED on the value raster's own grid: a pixel
+ * belongs to a polygon when its centre does; no result of GDAL is compared).  Coordinates are raster pixels: the raster spans
+ * [0, W] x [0, H], pixel (x, y) has its centre at (x + 1/2, y + 1/2); they are held as int32 fixed point with 8 fractional bits,
+ * X = round_half_even(256 px), |X|, |Y| <= 2^29.  A zone is the set of the edges (X0, Y0, X1, Y1) of all rings of all its parts, closing
+ * segments included; horizontal edges may be left out (they never cross a scanline and are skipped).  With cy = 256 y + 128 and
+ * cx = 256 x + 128 an edge CROSSES row y when min(Y0, Y1) <= cy < max(Y0, Y1); its abscissa there is the rational
+ * xc = X0 + (cy - Y0)(X1 - X0) / (Y1 - Y0); pixel (x, y) is IN THE ZONE iff the number of crossing edges with xc > cx is odd.  Even-odd
+ * over all edges: exterior rings, holes and parts carry no flag, and where two parts overlap the overlap is outside.  A centre exactly on
+ * a left or top boundary is in, on a right or bottom boundary out, so two zones that share an edge never both own a pixel and never
+ * both miss it.  Integer form: oriented so that den = Y1 - Y0 > 0, with N = X0 den + (cy - Y0)(X1 - X0), a crossing toggles exactly the
+ * pixels x < t, t = ceil((N - 128 den) / (256 den)).  Differences stay <= 2^30 and every product below 2^61: int64 holds them; no float
+ * touches the rule.
+ *
+ * Tables, int32 on the device:
+ *   edges    [E][4]   (X0, Y0, X1, Y1), aligned to 16 bytes; an edge with a coordinate beyond +-2^29 contributes nothing
+ *   edge_off [Z + 1]  zone z owns edges[edge_off[z] .. edge_off[z + 1]); a range outside [0, E] is an empty zone
+ *   items    [NI][5]  (zone, xoff, yoff, xcount, ycount): a band of a zone's bounding box in raster pixels, clipped to the raster like a
+ *                     row of pos; a zone index outside [0, Z) does nothing.  A zone's items must not overlap and must cover every pixel
+ *                     of it that is to count (city_zones.zone_items cuts them)
+ *   item_off [Z + 1]  zone z's partials are those of items[item_off[z] .. item_off[z + 1]); a range outside [0, NI] gives zeros
+ * One workgroup of 256 lanes per item.  Per batch of rows and segment of <= 8192 columns: the lanes take the zone's edges in turn, one
+ * 16-byte load each; an edge toggles, in each row it crosses, one bit of an LDS bitmap (an LDS XOR atomic; t of the first row by one
+ * 64-bit floor division, quotient and remainder stepped exactly from row to row); a suffix XOR along the rows turns toggles into the
+ * in-zone mask; the batch is then walked in 16-byte groups as srbh_window_sums walks a window, the zone's bits ANDed into the selection,
+ * a group without a pixel in the zone loading nothing.  Cost follows the items, not the raster.  Wrong tables may give wrong sums; they
+ * never give a load outside the rasters' rows or the tables' own bytes, nor a store outside out / ws.  No global atomics, no host
+ * synchronisation, integers only: exact and bit-equal between runs.
+ *
+ * srbh_zone_sums: out int64 [Z][5] on the device, OVERWRITTEN: { count, n, sum, sumsq, max } per zone -- count = the zone's pixels inside
+ * the raster, the others over the selected pixels (0 when n == 0), overflow as for srbh_window_sums.  Each item's partials go to its slot
+ * of ws (srbh_zone_sums_ws_bytes(NI) bytes, no initialisation needed); a second kernel adds each zone's slots in item order.  A zone
+ * without items gives zeros.
+ * srbh_zone_hist: hist int64 [Z][nbins], OVERWRITTEN: per zone the selected pixels counted by min(v / bin_width, nbins - 1) with
+ * srbh_value_hist's multiply-shift; 1 <= bin_width <= 65535, 1 <= nbins <= 4096; a 32-bit LDS histogram per item goes to its slot of ws
+ * (srbh_zone_hist_ws_bytes(NI, nbins) bytes), the second kernel adds the slots in item order.
+ * The _ws_bytes queries are host only and return 0 for arguments the call would refuse.
+ * Refused with SRBH_ERR_ARG, nothing launched: whatever srbh_window_sums refuses; a null table, out or ws; Z, E or NI <= 0; edges not
+ * aligned to 16 bytes, out or ws not to 8; bin_width or nbins out of range. */
+size_t srbh_zone_sums_ws_bytes(int NI);
+size_t srbh_zone_hist_ws_bytes(int NI, int nbins);
+int srbh_zone_sums(const void* v, int typeV, long row_strideV, const void* m, int typeM, long row_strideM, int H, int W,
+                   const int* edges, const int* edge_off, int Z, int E, const int* items, const int* item_off, int NI, int vthr, int mthr,
+                   long long* out, void* ws, void* stream);
+int srbh_zone_hist(const void* v, int typeV, long row_strideV, const void* m, int typeM, long row_strideM, int H, int W,
+                   const int* edges, const int* edge_off, int Z, int E, const int* items, const int* item_off, int NI, int vthr, int mthr,
+                   int bin_width, int nbins, long long* hist, void* ws, void* stream);
+
 /* ---- The middle of an MBConv block in ONE launch per direction (round 4; efficientnet_pytorch MBConvBlock.forward between the expand and
  * the project conv, run by smp's encoder at mymodels.py:276): BatchNorm0 (training) + SiLU -> depthwise KxK, stride 1, "same" zero padding ->
  * BatchNorm1 (training) + SiLU (+ the plane means squeeze-and-excitation pools).  fp32 NCHW, square planes 2x2 / 4x4 / 8x8, K = 3 | 5.

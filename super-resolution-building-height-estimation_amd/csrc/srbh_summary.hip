@@ -21,49 +21,10 @@
 // Overflow.  A group holds at most 16 values below 2^16: its sum stays below 2^20 and is formed in 32 bits; everything a lane keeps
 // across groups is 64-bit.  v * v reaches (2^16 - 1)^2 < 2^32: the product is a 32 x 32 -> 64-bit multiply-add (one v_mad_u64_u32), so
 // the sum of squares is 64-bit from the first add; H * W < 2^31 keeps it below 2^31 * 2^32 = 2^63.  Counts: int32, below H * W.
-#include "srbh_raster_walk.h"
+#include "srbh_summary_select.h"
 
 namespace {
 using namespace srbh;
-
-struct SumParams {
-    Rasters r;                      // a: the values v, b: the mask m
-    int vthr, mthr;
-};
-
-struct Acc {
-    int n;
-    unsigned mx;
-    unsigned long long sum, sq;
-    __device__ __forceinline__ Acc down(int o) const { return {__shfl_down(n, o, 64), __shfl_down(mx, o, 64), __shfl_down(sum, o, 64), __shfl_down(sq, o, 64)}; }
-    __device__ __forceinline__ void merge(const Acc& o) {
-        n += o.n;
-        sum += o.sum;
-        sq += o.sq;
-        mx = mx > o.mx ? mx : o.mx;
-    }
-};
-
-// The selection rule on one group: wv = the words of its P values of v, and bit j of the result: pixel j of the group is selected.  The
-// value group is thresholded before the mask group is loaded.
-template <int EV, int EM>
-__device__ __forceinline__ unsigned select_group(const SumParams& p, const Group<EV, EM>& g, unsigned* wv) {
-    using G = Group<EV, EM>;
-    g.load_a(wv);
-    unsigned sel = 0;
-#pragma unroll
-    for (int j = 0; j < G::P; ++j) sel |= ((int)group_pixel<EV>(wv, j) > p.vthr ? 1u : 0u) << j;
-    sel &= g.inside();
-    if (EM) {
-        unsigned wm[G::WORDS_B];
-        g.load_b(wm);
-        unsigned ms = 0;
-#pragma unroll
-        for (int j = 0; j < G::P; ++j) ms |= ((int)group_pixel<G::EBB>(wm, j) > p.mthr ? 1u : 0u) << j;
-        sel &= ms;
-    }
-    return sel;
-}
 
 // the selected pixels of the rectangle [x0, x1) x [y0, y0 + rows) that lane `tid` of `team` walks, added to a
 template <int EV, int EM>
@@ -127,14 +88,9 @@ __global__ __launch_bounds__(256) void block_sums_kernel(const SumParams p, int 
 }
 
 // ---- histogram ----------------------------------------------------------------------------------------------------------------------------
-constexpr int VH_MAX_BINS = 4096;
 constexpr int VH_MAX_WGS = 2048;
 constexpr int VH_GROUPS_PER_LANE = 8;                  // a workgroup is worth launching for 256 * 8 groups of 16 bytes
 
-// v / d for 0 <= v < 2^16, 2 <= d < 2^16 is (v * M) >> 32 with M = floor(2^32 / d) + 1: M d = 2^32 + e with 0 < e <= d, so
-// v M / 2^32 = v / d + v e / (d 2^32), and v e <= (2^16 - 1)^2 < 2^32 adds less than 1 / d: the floor does not move.  d == 1 would need
-// M = 2^32 + 1, which 32 bits do not hold: magic 0 stands for it, and the quotient is v.
-inline unsigned vh_magic(int d) { return d >= 2 && d <= 65535 ? (unsigned)(0x100000000ull / (unsigned)d) + 1u : 0u; }
 inline long vh_wgs(int H, int W) {
     const long groups = (long)H * (((long)W + 14) / 8 + 1);           // not below the (row, group) pairs of either element size
     const long wgs = (groups + 256L * VH_GROUPS_PER_LANE - 1) / (256L * VH_GROUPS_PER_LANE);
@@ -184,20 +140,6 @@ __global__ __launch_bounds__(256) void value_hist_fold_kernel(const unsigned* __
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------------
-inline bool sum_type_ok(int type) { return type == SRBH_GRID_U16 || type == SRBH_GRID_U8; }
-
-// the checks common to the three entries; fills p.  SRBH_OK or SRBH_ERR_ARG (the error text is set)
-int sum_params(const char* who, const void* v, int typeV, long rsV, const void* m, int typeM, long rsM, int H, int W, int vthr, int mthr,
-               SumParams* p) {
-    SRBH_REQUIRE(sum_type_ok(typeV) && (!m || sum_type_ok(typeM)),
-                 "%s: element type typeV=%d typeM=%d; the rasters are uint16 (1) or uint8 (3) -- int16, float32 and unknown codes are refused",
-                 who, typeV, typeM);
-    SRBH_REQUIRE(vthr >= -1 && vthr <= 65535 && mthr >= -1 && mthr <= 65535, "%s: a threshold (vthr=%d, mthr=%d) outside -1..65535", who,
-                 vthr, mthr);
-    p->vthr = vthr; p->mthr = mthr;
-    return rasters_checked(who, v, typeV, rsV, m, typeM, rsM, H, W, &p->r);
-}
-
 }  // namespace
 
 extern "C" int srbh_window_sums(const void* v, int typeV, long row_strideV, const void* m, int typeM, long row_strideM, int H, int W,

@@ -1,0 +1,305 @@
+// srbh_zones.hip -- polygon zones over a city's rasters: the reference's "mean and std of building height in each urban center"
+// (datasetglobe/urbanarea_meanstd.xls, README "Testing on 301 urban centers") is one gdal.RasterizeLayer into a scratch raster, one window
+// read and one numpy.ma sum per feature (zonal_stats, demo_preprocess_height_v2.py:450-570).  Here the zones are rasterised on the device,
+// row by row into an LDS bitmap that is never stored, and summed under the selection rule of srbh_summary.hip in exact integers.
+//
+// The rule (include/srbh.h states it in full).  Vertices are int32 fixed point with 8 fractional bits in raster pixel coordinates, a zone
+// is the set of its non-horizontal edges (X0, Y0, X1, Y1).  With cy = 256 y + 128 and cx = 256 x + 128 an edge CROSSES row y when
+// min(Y0, Y1) <= cy < max(Y0, Y1); pixel (x, y) is in the zone iff the number of crossing edges whose abscissa xc on the scanline is
+// > cx is odd.  Oriented so that den = Y1 - Y0 > 0, a crossing toggles exactly the pixels x < t,
+//   t = ceil((N - 128 den) / (256 den)) = floor((N + 128 den - 1) / (256 den)),   N = X0 den + (cy - Y0)(X1 - X0).
+// |X|, |Y| <= 2^29: den and |X1 - X0| stay <= 2^30, |N| <= 2^59 + 2^60, everything fits int64.  No floating point touches the rule.
+//
+// Work is a list of ITEMS (zone, xoff, yoff, xcount, ycount): horizontal bands of a zone's bounding box, one workgroup of 256 lanes each.
+// A band is done in batches of rows x segments of columns that fit the bitmap (BM_WORDS words; a row of a segment is wpr <= 256 words):
+//   1. the lanes take the zone's edges in turn (one 16-byte load each); an edge walks the batch's rows it crosses -- t of its first row by
+//      one 64-bit floor division, then quotient and remainder stepped row by row, exactly -- and toggles bit min(t, xe) - 1 - xs of the row
+//      by an LDS XOR atomic (t <= xs toggles no pixel of the segment, t >= xe all of them);
+//   2. an inclusive suffix XOR along each row turns the toggles into the in-zone mask: within a word by shifts, across words by the parity
+//      of the popcounts to the right (a ballot per 64 words);
+//   3. walk_rect walks the batch; a group's row is recovered from its row pointer (an exact division by the row stride: a multiplication
+//      by the stride's inverse modulo 2^64), the zone's bits of its P columns are ANDed into the selection.  A group with no pixel in the
+//      zone loads nothing.
+// Loads of the rasters are walk_rect's: the memory-safety argument of srbh_raster_walk.h carries over untouched.  The tables are read
+// through checked indices only, so no content of theirs leads outside them, the rasters' rows, ws or out.  No global atomics, no host
+// synchronisation; per-item partials go to ws and a second kernel adds each zone's items in item order.
+#include "srbh_summary_select.h"
+
+namespace {
+using namespace srbh;
+
+constexpr int BM_WORDS = 2048;                          // the bitmap: 64 Ki pixels of a batch
+constexpr int BM_MAX_WPR = 256;                         // words of a row of one segment: 8192 columns
+constexpr int COORD_MAX = 1 << 29;
+
+struct ZoneTables {
+    const int4* edges;              // [E] (X0, Y0, X1, Y1)
+    const int* edge_off;            // [Z + 1]
+    const int* items;               // [NI][5] (zone, xoff, yoff, xcount, ycount)
+    const int* item_off;            // [Z + 1]
+    int Z, E, NI;
+    int row_tz;                     // the value raster's row stride in bytes = row_odd << row_tz,
+    unsigned long long row_inv;     // row_inv * row_odd == 1 modulo 2^64
+};
+
+struct ZAcc {
+    int cnt;
+    Acc a;
+    __device__ __forceinline__ ZAcc down(int o) const { return {__shfl_down(cnt, o, 64), a.down(o)}; }
+    __device__ __forceinline__ void merge(const ZAcc& o) { cnt += o.cnt; a.merge(o.a); }
+};
+
+// floor(a / b) for b > 0, the remainder in [0, b) to *r
+__device__ __forceinline__ long long floor_div(long long a, long long b, long long* r) {
+    long long q = a / b, m = a - q * b;
+    if (m < 0) { m += b; --q; }
+    *r = m;
+    return q;
+}
+
+// step 1: the toggles of the zone's edges [e0, e1) in the rows [yb, yb + rb) and the columns [xs, xe); bm holds rb rows of wpr words, zeroed
+__device__ __forceinline__ void toggle_edges(const int4* __restrict__ edges, int e0, int e1, int yb, int rb, int xs, int xe, int wpr, unsigned* bm) {
+    for (int e = e0 + (int)threadIdx.x; e < e1; e += 256) {
+        const int4 q = edges[e];
+        int X0 = q.x, Y0 = q.y, X1 = q.z, Y1 = q.w;
+        const bool ok = X0 >= -COORD_MAX && X0 <= COORD_MAX && X1 >= -COORD_MAX && X1 <= COORD_MAX && Y0 >= -COORD_MAX && Y0 <= COORD_MAX &&
+                        Y1 >= -COORD_MAX && Y1 <= COORD_MAX;
+        if (!ok || Y0 == Y1) continue;
+        if (Y0 > Y1) { int s = X0; X0 = X1; X1 = s; s = Y0; Y0 = Y1; Y1 = s; }
+        // the rows with Y0 <= 256 y + 128 < Y1
+        int ya = (Y0 + 127) >> 8, ye = (Y1 + 127) >> 8;
+        ya = ya > yb ? ya : yb;
+        ye = ye < yb + rb ? ye : yb + rb;
+        if (ya >= ye) continue;
+        const long long den = (long long)Y1 - Y0, dx = (long long)X1 - X0, D = 256 * den;
+        long long r, sr;
+        long long t = floor_div(X0 * den + (256ll * ya + 128 - Y0) * dx + 128 * den - 1, D, &r);
+        const long long st = floor_div(256 * dx, D, &sr);
+        for (int y = ya; y < ye; ++y) {
+            if (t > xs) {
+                const int j = (int)(t < xe ? t : xe) - 1 - xs;
+                atomicXor(&bm[(y - yb) * wpr + (j >> 5)], 1u << (j & 31));
+            }
+            t += st;
+            r += sr;
+            if (r >= D) { r -= D; ++t; }
+        }
+    }
+}
+
+// step 2: every row of bm (rb rows of wpr words) replaced by its inclusive suffix XOR: bit i = the XOR of the bits >= i of the row.  A wave
+// takes 64 / G rows at a time, G = the power of two >= wpr (64 for wider rows, which go 64 words at a time from the right).
+__device__ __forceinline__ void suffix_xor_rows(unsigned* bm, int rb, int wpr) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int lg = 6;
+    while (lg > 0 && (1 << (lg - 1)) >= wpr) --lg;
+    const int G = 1 << lg, R = 64 >> lg, sub = lane >> lg, j = lane & (G - 1);
+    const int chunks = (wpr + 63) >> 6;
+    for (int r0 = wave * R; r0 < rb; r0 += 4 * R) {                   // uniform in a wave
+        const int row = r0 + sub;
+        unsigned carry = 0;
+        for (int c = chunks - 1; c >= 0; --c) {
+            const int w = c * 64 + j;
+            const bool on = row < rb && w < wpr;
+            unsigned v = on ? bm[row * wpr + w] : 0u;
+            const unsigned long long par = __ballot(__popc(v) & 1);
+            const unsigned long long mine = lg == 6 ? par : (par >> (sub * G)) & ((1ull << G) - 1ull);
+            const unsigned right = (unsigned)__popcll((mine >> j) >> 1) & 1u;      // the words of this row to the right of w
+            v ^= v >> 1; v ^= v >> 2; v ^= v >> 4; v ^= v >> 8; v ^= v >> 16;
+            if (right ^ carry) v = ~v;
+            if (on) bm[row * wpr + w] = v;
+            carry ^= (unsigned)__popcll(mine) & 1u;
+        }
+    }
+}
+
+// One item.  HIST == false: {count, n, sum, sumsq, max} to ws int64 [NI][5]; HIST == true: the item's histogram to ws uint32 [NI][nbins].
+template <int EV, int EM, bool HIST>
+__global__ __launch_bounds__(256) void zone_item_kernel(const SumParams p, const ZoneTables z, unsigned magic, int nbins, void* __restrict__ ws) {
+    using G = Group<EV, EM>;
+    __shared__ unsigned bm[BM_WORDS + 1];                             // (+ 1: a group's bits are read as a pair of words)
+    __shared__ unsigned hist[HIST ? VH_MAX_BINS : 1];
+    const int t = threadIdx.x;
+    const long item = blockIdx.x;                                     // < NI
+    const int* q = z.items + 5 * item;
+    const int zone = q[0];
+    const Rect w = clip_window(q + 1, p.r.H, p.r.W);
+    int e0 = 0, e1 = 0;
+    if (zone >= 0 && zone < z.Z) {
+        const int a = z.edge_off[zone], b = z.edge_off[zone + 1];
+        if (a >= 0 && a <= b && b <= z.E) { e0 = a; e1 = b; }
+    }
+    if (HIST) {
+        for (int i = t; i < nbins; i += 256) hist[i] = 0u;
+    }
+    if (t == 0) bm[BM_WORDS] = 0u;
+    ZAcc acc = {0, {0, 0u, 0ull, 0ull}};
+    const unsigned last = (unsigned)nbins - 1u;
+    if (w.any && e1 > e0) {                                           // uniform
+        const int width = w.x1 - w.x0;
+        const int full = (int)(((long)width + 31) >> 5);
+        const int wpr = full < BM_MAX_WPR ? full : BM_MAX_WPR, segw = wpr * 32, rbmax = BM_WORDS / wpr;
+        for (long done = 0; done < w.rows; done += rbmax) {
+            const int yb = w.y0 + (int)done, left = w.rows - (int)done, rb = left < rbmax ? left : rbmax;
+            for (long xl = w.x0; xl < w.x1; xl += segw) {
+                const int xs = (int)xl, xe = xl + segw < w.x1 ? (int)(xl + segw) : w.x1;
+                __syncthreads();                                      // the walk before is done with bm
+                for (int i = t; i < rb * wpr; i += 256) bm[i] = 0u;
+                __syncthreads();
+                toggle_edges(z.edges, e0, e1, yb, rb, xs, xe, wpr, bm);
+                __syncthreads();
+                suffix_xor_rows(bm, rb, wpr);
+                __syncthreads();
+                walk_rect<EV, EM>(p.r, xs, xe, yb, rb, t, 256, [&](const G& g) {
+                    const int row = (int)(((unsigned long long)(g.rowA - p.r.a) >> z.row_tz) * z.row_inv) - yb;      // in [0, rb)
+                    const unsigned* brow = bm + row * wpr;
+                    const int off = g.c0 - xs;                        // in (-P, segw)
+                    unsigned zb;
+                    if (off >= 0) {
+                        const unsigned long long pair = brow[off >> 5] | ((unsigned long long)brow[(off >> 5) + 1] << 32);
+                        zb = (unsigned)(pair >> (off & 31));
+                    } else {
+                        zb = brow[0] << -off;
+                    }
+                    zb &= g.inside();                                 // (bits beyond xe belong to the next row or are the suffix's spill)
+                    if (!zb) return;
+                    unsigned wv[G::WORDS_A];
+                    const unsigned sel = select_group(p, g, wv) & zb;
+                    if (HIST) {
+#pragma unroll
+                        for (int j = 0; j < G::P; ++j) {
+                            if ((sel >> j) & 1u) {
+                                const unsigned v = group_pixel<EV>(wv, j), qv = magic ? __umulhi(v, magic) : v;
+                                atomicAdd(&hist[qv < last ? qv : last], 1u);
+                            }
+                        }
+                    } else {
+                        acc.cnt += __popc(zb);
+                        add_group<EV>(acc.a, sel, wv);
+                    }
+                });
+            }
+        }
+    }
+    if (HIST) {
+        __syncthreads();
+        unsigned* o = (unsigned*)ws + item * nbins;
+        for (int i = t; i < nbins; i += 256) o[i] = hist[i];
+    } else {
+        fold_team<256>(acc);
+        if (t == 0) {
+            long long* o = (long long*)ws + 5 * item;
+            o[0] = acc.cnt;
+            o[1] = acc.a.n;
+            o[2] = (long long)acc.a.sum;
+            o[3] = (long long)acc.a.sq;
+            o[4] = acc.a.mx;
+        }
+    }
+}
+
+// the items [i0, i1) of zone z, or none where item_off does not lie inside [0, NI]
+__device__ __forceinline__ void zone_items(const ZoneTables& z, int zone, int* i0, int* i1) {
+    const int a = z.item_off[zone], b = z.item_off[zone + 1];
+    const bool ok = a >= 0 && a <= b && b <= z.NI;
+    *i0 = ok ? a : 0;
+    *i1 = ok ? b : 0;
+}
+
+// a lane per zone: its items' partials added in item order
+__global__ __launch_bounds__(256) void zone_sums_fold_kernel(const ZoneTables z, const long long* __restrict__ ws, long long* __restrict__ out) {
+    const long zone = blockIdx.x * 256L + threadIdx.x;
+    if (zone >= z.Z) return;
+    int i0, i1;
+    zone_items(z, (int)zone, &i0, &i1);
+    long long s[5] = {0, 0, 0, 0, 0};
+    for (int i = i0; i < i1; ++i) {
+        const long long* a = ws + 5 * (long)i;
+        s[0] += a[0]; s[1] += a[1]; s[2] += a[2]; s[3] += a[3];
+        s[4] = s[4] > a[4] ? s[4] : a[4];
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k) out[5 * zone + k] = s[k];
+}
+
+// block (zone, 256 bins): a lane per bin
+__global__ __launch_bounds__(256) void zone_hist_fold_kernel(const ZoneTables z, int nbins, const unsigned* __restrict__ ws, long long* __restrict__ hist) {
+    const int zone = blockIdx.x, bin = blockIdx.y * 256 + threadIdx.x;
+    if (bin >= nbins) return;
+    int i0, i1;
+    zone_items(z, zone, &i0, &i1);
+    long long s = 0;
+    for (int i = i0; i < i1; ++i) s += ws[(long)i * nbins + bin];
+    hist[(long)zone * nbins + bin] = s;
+}
+
+// ---- host -----------------------------------------------------------------------------------------------------------------------------------
+int zone_tables(const char* who, const int* edges, const int* edge_off, int Z, int E, const int* items, const int* item_off, int NI,
+                const SumParams& p, int typeV, ZoneTables* z) {
+    SRBH_REQUIRE(edges && edge_off && items && item_off, "%s: null table", who);
+    SRBH_REQUIRE(Z > 0 && E > 0 && NI > 0, "%s: Z=%d, E=%d and the item count %d must be positive", who, Z, E, NI);
+    SRBH_REQUIRE((uintptr_t)edges % 16 == 0 && (uintptr_t)edge_off % 4 == 0 && (uintptr_t)items % 4 == 0 && (uintptr_t)item_off % 4 == 0,
+                 "%s: edges must be aligned to 16 bytes, the other tables to 4", who);
+    z->edges = (const int4*)edges; z->edge_off = edge_off; z->items = items; z->item_off = item_off;
+    z->Z = Z; z->E = E; z->NI = NI;
+    unsigned long long s = (unsigned long long)p.r.rsA * (unsigned)raster_esz(typeV);      // > 0
+    z->row_tz = __builtin_ctzll(s);
+    s >>= z->row_tz;
+    unsigned long long inv = s;                                       // correct to 3 bits; each step doubles them
+    for (int i = 0; i < 5; ++i) inv *= 2ull - s * inv;
+    z->row_inv = inv;
+    return SRBH_OK;
+}
+
+template <bool HIST>
+int zone_launch(const char* who, const void* v, int typeV, long rsV, const void* m, int typeM, long rsM, int H, int W, const int* edges,
+                const int* edge_off, int Z, int E, const int* items, const int* item_off, int NI, int vthr, int mthr, int bin_width, int nbins,
+                long long* out, void* ws, void* stream) {
+    SRBH_REQUIRE(out && ws, "%s: null pointer", who);
+    if (HIST) {
+        SRBH_REQUIRE(bin_width >= 1 && bin_width <= 65535, "%s: bin_width=%d outside 1..65535", who, bin_width);
+        SRBH_REQUIRE(nbins >= 1 && nbins <= VH_MAX_BINS, "%s: nbins=%d outside 1..%d", who, nbins, VH_MAX_BINS);
+    }
+    SumParams p;
+    int rc = sum_params(who, v, typeV, rsV, m, typeM, rsM, H, W, vthr, mthr, &p);
+    if (rc != SRBH_OK) return rc;
+    ZoneTables z;
+    rc = zone_tables(who, edges, edge_off, Z, E, items, item_off, NI, p, typeV, &z);
+    if (rc != SRBH_OK) return rc;
+    SRBH_REQUIRE((uintptr_t)ws % 8 == 0 && (uintptr_t)out % 8 == 0, "%s: out and ws must be aligned to 8 bytes", who);
+    const unsigned magic = HIST ? vh_magic(bin_width) : 0u;
+    hipStream_t st = (hipStream_t)stream;
+    with_sizes(typeV, m, typeM, [&](auto ev, auto em) {
+        hipLaunchKernelGGL((zone_item_kernel<decltype(ev)::value, decltype(em)::value, HIST>), dim3((unsigned)NI), dim3(256), 0, st, p, z, magic,
+                           HIST ? nbins : 1, ws);
+    });
+    SRBH_HIP(hipGetLastError());
+    if (HIST)
+        hipLaunchKernelGGL(zone_hist_fold_kernel, dim3((unsigned)Z, (unsigned)((nbins + 255) / 256)), dim3(256), 0, st, z, nbins, (const unsigned*)ws, out);
+    else
+        hipLaunchKernelGGL(zone_sums_fold_kernel, dim3((unsigned)((Z + 255L) / 256)), dim3(256), 0, st, z, (const long long*)ws, out);
+    SRBH_HIP(hipGetLastError());
+    return SRBH_OK;
+}
+
+}  // namespace
+
+extern "C" size_t srbh_zone_sums_ws_bytes(int NI) { return NI > 0 ? (size_t)NI * 5 * sizeof(long long) : 0; }
+
+extern "C" size_t srbh_zone_hist_ws_bytes(int NI, int nbins) {
+    return NI > 0 && nbins >= 1 && nbins <= VH_MAX_BINS ? (size_t)NI * nbins * sizeof(unsigned) : 0;
+}
+
+extern "C" int srbh_zone_sums(const void* v, int typeV, long row_strideV, const void* m, int typeM, long row_strideM, int H, int W,
+                              const int* edges, const int* edge_off, int Z, int E, const int* items, const int* item_off, int NI, int vthr,
+                              int mthr, long long* out, void* ws, void* stream) {
+    return zone_launch<false>("srbh_zone_sums", v, typeV, row_strideV, m, typeM, row_strideM, H, W, edges, edge_off, Z, E, items, item_off, NI,
+                              vthr, mthr, 1, 1, out, ws, stream);
+}
+
+extern "C" int srbh_zone_hist(const void* v, int typeV, long row_strideV, const void* m, int typeM, long row_strideM, int H, int W,
+                              const int* edges, const int* edge_off, int Z, int E, const int* items, const int* item_off, int NI, int vthr,
+                              int mthr, int bin_width, int nbins, long long* hist, void* ws, void* stream) {
+    return zone_launch<true>("srbh_zone_hist", v, typeV, row_strideV, m, typeM, row_strideM, H, W, edges, edge_off, Z, E, items, item_off, NI,
+                             vthr, mthr, bin_width, nbins, hist, ws, stream);
+}
