@@ -1,5 +1,6 @@
 // srbh_dwconv.hip -- depthwise KxK convolution (K = 3 or 5, stride 1 or 2), fp32 NCHW, forward / input gradient / weight
-// gradient, with the zero padding folded in (top/left pad given; bottom/right implied by the output size).
+// gradient, with the zero padding folded in (top/left pad given; bottom/right implied by the output size), and the fused
+// inference form of the MBConv middle.  (The encoder's other inference kernels: srbh_enc_eval.hip.)
 //
 // Why it exists: the EfficientNet-B4 encoder the reference instantiates (mymodels.py:242-248) is stock PyTorch ops in
 // this build, but MIOpen has no fp32 solver for its 5x5 / strided depthwise convolutions and falls back
@@ -12,7 +13,8 @@
 
 namespace {
 using namespace srbh;
-typedef float floatx4 __attribute__((ext_vector_type(4)));
+
+#include "srbh_dw_pieces.h"      // act_apply, wave_sum, DWLds, dw_stage, grid_for
 
 struct DWParams {
     const float* x;     // [B][C][H][W]
@@ -22,6 +24,10 @@ struct DWParams {
     int B, C, H, W, OH, OW, stride, pad_t, pad_l;
 };
 
+// (What stays written out although it repeats -- profiles/dw_pieces_isa.txt, "tried and left out": the tap loops of every kernel, the
+//  two-accumulator walk over LDS in dw_lds_kernel and dw_lds_eval_kernel included -- as a shared piece it cost dw_lds_kernel<5, *> 24 VGPRs
+//  and three of its eight waves per SIMD; and the reduction tail of the two weight-gradient kernels -- as a shared piece
+//  dw_bwd_weight_kernel<3> measured 0.4 % above the parent at 144 x 32 x 32, stride 2, and even wave_sum() inside it gives other code.)
 template <int K>
 __global__ __launch_bounds__(256) void dw_fwd_kernel(const DWParams p) {
     const long total = (long)p.B * p.C * p.OH * p.OW;
@@ -82,8 +88,7 @@ __global__ __launch_bounds__(256) void dw_bwd_data_kernel(const DWParams p) {
 
 // dw[c][i][j] = sum over (b, oy, ox) of dy[b][c][oy][ox] * x[b][c][oy*s - pad_t + i][ox*s - pad_l + j]: workgroup (c, s)
 // sums the images of batch slice s in a fixed tree (thread-strided partial sums -> wave shuffles -> LDS across the 4
-// waves) into ws[s][c][..]; dw_reduce_kernel adds the slices in order: deterministic, and >= ~1000 workgroups even for the
-// 144-channel layers
+// waves) into ws[s][c][..]; dw_reduce_kernel adds the slices in order: deterministic, and >= ~1000 workgroups even for the 144-channel layers
 template <int K>
 __global__ __launch_bounds__(256) void dw_bwd_weight_kernel(const DWParams p, float* __restrict__ ws, int splits) {
     const int c = blockIdx.x, sp = blockIdx.y;
@@ -125,39 +130,17 @@ __global__ __launch_bounds__(256) void dw_bwd_weight_kernel(const DWParams p, fl
         ws[((long)sp * p.C + c) * K * K + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
 
-// ---- LDS-staged forms (round 3).  The one-thread-per-output kernels above spend ~150 instructions per output on 25 predicated taps with 64-bit
-// address arithmetic (13-25 us per call on tensors that take 3-5 us to stream); here a workgroup stages P whole planes ZERO-PADDED in LDS
-// (coalesced reads of P contiguous planes), so every tap is one unconditional ds_read + fma.
-//   forward        : out[oy][ox] = sum_ij xpad[oy s + i][ox s + j] w[i][j]                      (x placed at (pad_t, pad_l))
-//   input gradient : dx[y][x]   = sum_ij dyup[y + pad_t + K-1 - i][x + pad_l + K-1 - j] w[i][j]  (dy placed at (K-1 + oy s, K-1 + ox s): zero-upsampled)
-struct DWLds {
-    const float* src; const float* w; float* out;
-    long planes;
-    int C, SH, SW, OUTH, OUTW, PH, PW, ss, soy, sox, os, by, bx, P;
-};
+// forward (FLIP = 0) and input gradient (FLIP = 1) over staged planes: thread = one output, even and odd taps in two accumulators
 template <int K, int FLIP>
 __global__ __launch_bounds__(256) void dw_lds_kernel(const DWLds p) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    const int t = threadIdx.x, plane_sz = p.PH * p.PW;
+    const int plane_sz = p.PH * p.PW;
     float* wl = sm + p.P * plane_sz;
     const long p0 = (long)blockIdx.x * p.P;
-    const int np = (int)((p.planes - p0) < p.P ? (p.planes - p0) : p.P);
-    // (zero fill, then scatter the source elements: a single pass over the PADDED index space -- a division and a predicated gather per
-    //  padded element -- was measured slower on every shape)
-    for (int e = t; e < p.P * plane_sz; e += 256) sm[e] = 0.f;
-    for (int e = t; e < np * K * K; e += 256) wl[e] = p.w[(long)((p0 + e / (K * K)) % p.C) * K * K + e % (K * K)];
-    __syncthreads();
-    const int ssz = p.SH * p.SW;
-    const float* sp = p.src + p0 * ssz;
-    for (int e = t; e < np * ssz; e += 256) {
-        const int pl = e / ssz, q = e - pl * ssz, u = q / p.SW, v = q - u * p.SW;
-        const int r = u * p.ss + p.soy, c = v * p.ss + p.sox;
-        if (r < p.PH && c < p.PW) sm[pl * plane_sz + r * p.PW + c] = sp[e];
-    }
-    __syncthreads();
+    const int np = dw_stage<K, false>(p, sm, wl, p0, nullptr, nullptr);
     const int osz = p.OUTH * p.OUTW;
     float* op = p.out + p0 * osz;
-    for (int e = t; e < np * osz; e += 256) {
+    for (int e = threadIdx.x; e < np * osz; e += 256) {
         const int pl = e / osz, q = e - pl * osz, oy = q / p.OUTW, ox = q - oy * p.OUTW;
         const float* base = sm + pl * plane_sz + (oy * p.os + p.by) * p.PW + ox * p.os + p.bx;
         const float* wp = wl + pl * K * K;
@@ -186,7 +169,6 @@ struct DWEval {
     float* pooled;                         // [planes] means of the activated output
     int G;
 };
-__device__ __forceinline__ float silu_f(float u) { return u / (1.f + __expf(-u)); }
 template <int K>
 __global__ __launch_bounds__(256) void dw_lds_eval_kernel(const DWLds p, const DWEval q) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -194,23 +176,7 @@ __global__ __launch_bounds__(256) void dw_lds_eval_kernel(const DWLds p, const D
     const int t = threadIdx.x, plane_sz = p.PH * p.PW;
     float* wl = sm + p.P * plane_sz;
     const long p0 = (long)blockIdx.x * p.P;
-    const int np = (int)((p.planes - p0) < p.P ? (p.planes - p0) : p.P);
-    for (int e = t; e < p.P * plane_sz; e += 256) sm[e] = 0.f;
-    for (int e = t; e < np * K * K; e += 256) wl[e] = p.w[(long)((p0 + e / (K * K)) % p.C) * K * K + e % (K * K)];
-    __syncthreads();
-    const int ssz = p.SH * p.SW;
-    const float* sp = p.src + p0 * ssz;
-    for (int e = t; e < np * ssz; e += 256) {
-        const int pl = e / ssz, r0 = e - pl * ssz, u = r0 / p.SW, v = r0 - u * p.SW;
-        const int r = u * p.ss + p.soy, c = v * p.ss + p.sox;
-        float x = sp[e];
-        if (q.a0) {
-            const int ch = (int)((p0 + pl) % p.C);
-            x = silu_f(fmaf(x, q.a0[ch], q.b0[ch]));
-        }
-        if (r < p.PH && c < p.PW) sm[pl * plane_sz + r * p.PW + c] = x;
-    }
-    __syncthreads();
+    const int np = dw_stage<K, true>(p, sm, wl, p0, q.a0, q.b0);
     const int osz = p.OUTH * p.OUTW, G = q.G, g = t & (G - 1), slot = t / G, R = 256 / G;
     float* op = p.out + p0 * osz;
     const float inv = 1.f / (float)osz;
@@ -233,7 +199,7 @@ __global__ __launch_bounds__(256) void dw_lds_eval_kernel(const DWLds p, const D
                         if ((i * K + j) & 1) c1 = fmaf(base[i * p.PW + j], wp[i * K + j], c1);
                         else c0 = fmaf(base[i * p.PW + j], wp[i * K + j], c0);
                     }
-                const float y = silu_f(fmaf(c0 + c1, s, h));
+                const float y = act_apply(fmaf(c0 + c1, s, h), 1);
                 op[(long)pl * osz + o] = y;
                 sum += y;
             }
@@ -250,49 +216,6 @@ __global__ __launch_bounds__(256) void dw_lds_eval_kernel(const DWLds p, const D
                 q.pooled[p0 + pl] = tot * inv;
             }
             __syncthreads();
-        }
-    }
-}
-
-//  gate[b][c] = sigmoid(b2[c] + sum_j w2[c][j] * hidden[b][j]) on its own (the fused inference block multiplies it into the project conv's
-//  operand instead of rewriting the expanded tensor).  16 lanes share one channel: a wave walks 4 contiguous rows of w2 (coalesced; one
-//  thread per (b, c) read 64 different rows per load and ran 15 us), keeps its slice of the row in registers and loops over a chunk of
-//  images; fixed butterfly over the 16 lanes.
-constexpr int SE_GATE_IB = 8;          // images per workgroup row
-__global__ __launch_bounds__(256) void se_gate_kernel(const float* __restrict__ hidden, const float* __restrict__ w2, const float* __restrict__ b2,
-                                                     float* __restrict__ gate, int B, int C, int SQ) {
-    const int t = threadIdx.x, sub = t & 15;
-    const int c = blockIdx.x * 16 + (t >> 4);
-    const bool ok = c < C;
-    const float* wr = w2 + (long)(ok ? c : 0) * SQ;
-    const int b0 = blockIdx.y * SE_GATE_IB, b1 = b0 + SE_GATE_IB < B ? b0 + SE_GATE_IB : B;
-    const float bias = ok ? b2[c] : 0.f;
-    if (SQ <= 128) {
-        float wv[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) wv[u] = (ok && sub + 16 * u < SQ) ? wr[sub + 16 * u] : 0.f;
-        for (int b = b0; b < b1; ++b) {
-            const float* hr = hidden + (long)b * SQ;
-            float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-            for (int u = 0; u < 8; u += 2) {
-                a0 = fmaf(wv[u], sub + 16 * u < SQ ? hr[sub + 16 * u] : 0.f, a0);
-                a1 = fmaf(wv[u + 1], sub + 16 * (u + 1) < SQ ? hr[sub + 16 * (u + 1)] : 0.f, a1);
-            }
-            float acc = a0 + a1;
-#pragma unroll
-            for (int o = 1; o < 16; o <<= 1) acc += __shfl_xor(acc, o, 64);
-            if (ok && sub == 0) gate[(long)b * C + c] = 1.f / (1.f + __expf(-(acc + bias)));
-        }
-    } else {
-        for (int b = b0; b < b1; ++b) {
-            const float* hr = hidden + (long)b * SQ;
-            float acc = 0.f;
-            if (ok)
-                for (int j = sub; j < SQ; j += 16) acc = fmaf(wr[j], hr[j], acc);
-#pragma unroll
-            for (int o = 1; o < 16; o <<= 1) acc += __shfl_xor(acc, o, 64);
-            if (ok && sub == 0) gate[(long)b * C + c] = 1.f / (1.f + __expf(-(acc + bias)));
         }
     }
 }
@@ -336,9 +259,7 @@ __global__ __launch_bounds__(256) void dw_lds_wgrad_kernel(const DWParams p, flo
     const int lane = t & 63, wave = t >> 6;
 #pragma unroll
     for (int q = 0; q < K * K; ++q) {
-        float v = acc[q];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+        const float v = wave_sum(acc[q]);
         if (lane == 0) red[wave][q] = v;
     }
     __syncthreads();
@@ -351,219 +272,6 @@ __global__ void dw_reduce_kernel(const float* __restrict__ ws, float* __restrict
     float v = 0.f;
     for (int s = 0; s < splits; ++s) v += ws[(long)s * n + i];
     dw[i] = v;
-}
-
-// inference BatchNorm (+ activation) on NCHW fp32: y = act(x * scale[c] + shift[c]); act 0 none, 1 SiLU, 2 ReLU.  One pass,
-// float4 when the plane size allows (MIOpen's inference-BatchNorm kernel takes ~39 us per call whatever the tensor size,
-// 115 calls per batch in the encoder / decoders).
-template <int VEC>
-__global__ __launch_bounds__(256) void affine_act_nchw_kernel(const float* __restrict__ x, const float* __restrict__ scale,
-                                                             const float* __restrict__ shift, const float* __restrict__ res,
-                                                             float* __restrict__ y, long planes, int C, int hw, int act) {
-    const int per = hw / VEC;
-    const long total = planes * per;
-    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
-        const long pl = idx / per;
-        const int c = (int)(pl % C);
-        const float s = scale[c], h = shift[c];
-        float v[VEC];
-        if (VEC == 4) {
-            const floatx4 t = ((const floatx4*)x)[idx];
-            v[0] = t[0]; v[1 % VEC] = t[1]; v[2 % VEC] = t[2]; v[3 % VEC] = t[3];
-        } else {
-            v[0] = x[idx];
-        }
-#pragma unroll
-        for (int q = 0; q < VEC; ++q) {
-            float u = fmaf(v[q], s, h);
-            if (act == 1) u = u / (1.f + __expf(-u));
-            else if (act == 2) u = fmaxf(u, 0.f);
-            v[q] = u;
-        }
-        if (VEC == 4) {
-            floatx4 t = {v[0], v[1 % VEC], v[2 % VEC], v[3 % VEC]};
-            if (res) t += ((const floatx4*)res)[idx];          // the block's skip connection (MBConv: x = bn2(project(x)) + inputs)
-            ((floatx4*)y)[idx] = t;
-        } else {
-            y[idx] = res ? v[0] + res[idx] : v[0];
-        }
-    }
-}
-
-// ---- the encoder's STEM at inference (round 6): conv3x3 stride 2 (static "same" padding) Cin <= 16 -> Cout <= 64 + the folded BatchNorm + SiLU in
-// one pass on NCHW fp32 (smp EfficientNetEncoder.forward through mymodels.py:276: `_swish(_bn0(_conv_stem(x)))`).  MIOpen's solver search
-// (benchmark mode of the tiled-inference path) settles on an asm kernel that takes ~0.6 ms per 128-tile batch for this 0.9-GFLOP layer
-// (profiles/r05cd_predict_steady_kernel_stats.txt), followed by the affine pass.  Here: one thread per output pixel, all Cout accumulators
-// in registers, the weights transposed into LDS as [ci][tap][co] and read as wave-uniform ds_read_b128 broadcasts, input taps straight from
-// L1 (a 64 x 64 plane is 16 KB), outputs written plane by plane (coalesced along x).
-template <int CO4>
-__global__ __launch_bounds__(256) void stem_conv_eval_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ scale,
-                                                            const float* __restrict__ shift, float* __restrict__ y, int B, int Cin, int H, int W,
-                                                            int stride, int pt, int pl, int OH, int OW, int act) {
-    constexpr int CO = CO4 * 4;
-    extern __shared__ __attribute__((aligned(16))) float wl[];          // [Cin][9][CO]
-    const int Cout = CO;
-    for (int i = threadIdx.x; i < Cout * Cin * 9; i += 256) {
-        const int co = i / (Cin * 9), r = i - co * Cin * 9;             // OIHW: r = ci * 9 + tap
-        wl[r * CO + co] = w[i];
-    }
-    __syncthreads();
-    const long total = (long)B * OH * OW;
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const int ox = (int)(idx % OW);
-    const long t = idx / OW;
-    const int oy = (int)(t % OH), b = (int)(t / OH);
-    floatx4 acc[CO4];
-#pragma unroll
-    for (int q = 0; q < CO4; ++q) acc[q] = floatx4{0.f, 0.f, 0.f, 0.f};
-    const int iy0 = oy * stride - pt, ix0 = ox * stride - pl;
-    const float* xb = x + (long)b * Cin * H * W;
-    for (int ci = 0; ci < Cin; ++ci) {
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            const int iy = iy0 + tap / 3, ix = ix0 + tap % 3;
-            float v = 0.f;
-            if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) v = xb[((long)ci * H + iy) * W + ix];
-            const floatx4* wq = (const floatx4*)(wl + (ci * 9 + tap) * CO);
-#pragma unroll
-            for (int q = 0; q < CO4; ++q) acc[q] += wq[q] * v;
-        }
-    }
-    float* yb = y + ((long)b * Cout * OH + oy) * OW + ox;
-#pragma unroll
-    for (int q = 0; q < CO4; ++q)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int co = q * 4 + j;
-            float u = fmaf(acc[q][j], scale[co], shift[co]);
-            if (act == 1) u = u / (1.f + __expf(-u));
-            else if (act == 2) u = fmaxf(u, 0.f);
-            yb[(long)co * OH * OW] = u;
-        }
-}
-
-// ---- squeeze-and-excitation of an MBConv block at inference (efficientnet_pytorch MBConvBlock.forward: avg-pool -> 1x1
-// reduce -> swish -> 1x1 expand -> sigmoid -> scale), three launches instead of ~11 stock-op ones per block:
-//  (1) inference BatchNorm + SiLU of the depthwise output WITH the per-plane mean (one wave per (b, c) plane, <= 1024 px)
-__global__ __launch_bounds__(256) void affine_act_pool_kernel(const float* __restrict__ x, const float* __restrict__ scale,
-                                                             const float* __restrict__ shift, float* __restrict__ y,
-                                                             float* __restrict__ pooled, long planes, int C, int hw, int act) {
-    const int lane = threadIdx.x & 63;
-    const long pl = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (pl >= planes) return;
-    const int c = (int)(pl % C);
-    const float s = scale[c], h = shift[c];
-    const float* xp = x + pl * hw;
-    float* yp = y + pl * hw;
-    float sum = 0.f;
-    for (int i = lane; i < hw; i += 64) {
-        float u = fmaf(xp[i], s, h);
-        if (act == 1) u = u / (1.f + __expf(-u));
-        else if (act == 2) u = fmaxf(u, 0.f);
-        yp[i] = u;
-        sum += u;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o, 64);
-    if (lane == 0) pooled[pl] = sum / (float)hw;
-}
-
-//  (2) hidden[b][j] = swish(b1[j] + sum_c w1[j][c] * pooled[b][c]): one WAVE per (b, j) dot product (grid = B x SQ/4
-//      workgroups: a per-b workgroup looping over j ran 63 us -- a serial chain of dependent global loads)
-__global__ __launch_bounds__(256) void se_hidden_kernel(const float* __restrict__ pooled, const float* __restrict__ w1,
-                                                       const float* __restrict__ b1, float* __restrict__ hidden, int C, int SQ) {
-    const int b = blockIdx.x, lane = threadIdx.x & 63;
-    const int j = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (j >= SQ) return;
-    const float* wr = w1 + (long)j * C;
-    const float* pr = pooled + (long)b * C;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    int c = lane;
-    for (; c + 192 < C; c += 256) {
-        a0 = fmaf(wr[c], pr[c], a0);
-        a1 = fmaf(wr[c + 64], pr[c + 64], a1);
-        a2 = fmaf(wr[c + 128], pr[c + 128], a2);
-        a3 = fmaf(wr[c + 192], pr[c + 192], a3);
-    }
-    for (; c < C; c += 64) a0 = fmaf(wr[c], pr[c], a0);
-    float acc = (a0 + a1) + (a2 + a3);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-    if (lane == 0) {
-        const float u = acc + b1[j];
-        hidden[(long)b * SQ + j] = u / (1.f + __expf(-u));
-    }
-}
-
-//  (3) y[plane] *= sigmoid(b2[c] + sum_j w2[c][j] * hidden[b][j]): one wave per (b, c) plane computes its own gate (row c of
-//      the expand weight is read coalesced by the wave) and scales the plane in place
-__global__ __launch_bounds__(256) void se_gate_scale_kernel(float* __restrict__ y, const float* __restrict__ hidden,
-                                                           const float* __restrict__ w2, const float* __restrict__ b2, long planes,
-                                                           int C, int SQ, int hw) {
-    const int lane = threadIdx.x & 63;
-    const long pl = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (pl >= planes) return;
-    const int c = (int)(pl % C);
-    const long b = pl / C;
-    const float* wr = w2 + (long)c * SQ;
-    const float* hr = hidden + b * SQ;
-    float acc = 0.f;
-    for (int j = lane; j < SQ; j += 64) acc = fmaf(wr[j], hr[j], acc);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    const float g = 1.f / (1.f + __expf(-(acc + b2[c])));
-    float* yp = y + pl * hw;
-    for (int i = lane; i < hw; i += 64) yp[i] *= g;
-}
-
-// small planes (hw = 1 .. 32, a power of two): a wave per plane would be mostly empty lanes (4 of 64 at 2x2, 172 k waves per call);
-// planes are contiguous, so a wave takes 64 consecutive elements = 64 / hw whole planes and reduces inside hw-lane segments
-__global__ __launch_bounds__(256) void affine_act_pool_small_kernel(const float* __restrict__ x, const float* __restrict__ scale,
-                                                                   const float* __restrict__ shift, float* __restrict__ y,
-                                                                   float* __restrict__ pooled, long planes, int C, int hw, int act) {
-    const int lane = threadIdx.x & 63;
-    const long idx = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64 + lane;
-    const long pl = idx / hw;
-    float u = 0.f;
-    if (pl < planes) {
-        const int c = (int)(pl % C);
-        u = fmaf(x[idx], scale[c], shift[c]);
-        if (act == 1) u = u / (1.f + __expf(-u));
-        else if (act == 2) u = fmaxf(u, 0.f);
-        y[idx] = u;
-    }
-    for (int o = 1; o < hw; o <<= 1) u += __shfl_xor(u, o, 64);
-    if (pl < planes && (lane & (hw - 1)) == 0) pooled[pl] = u / (float)hw;
-}
-
-// gate + scale for planes of 4 / 16 / 64 / 256 elements: a workgroup takes 1024 consecutive elements (a float4 per thread); the hw / 4
-// threads that hold one plane compute its gate together (same reason)
-__global__ __launch_bounds__(256) void se_gate_scale_quad_kernel(float* __restrict__ y, const float* __restrict__ hidden,
-                                                                const float* __restrict__ w2, const float* __restrict__ b2, long planes,
-                                                                int C, int SQ, int hw) {
-    const int t = threadIdx.x, G = hw >> 2, sub = t & (G - 1);
-    const long e = (long)blockIdx.x * 1024 + 4 * t;
-    const long pl = e / hw;
-    const bool ok = pl < planes;
-    const int c = ok ? (int)(pl % C) : 0;
-    const long b = ok ? pl / C : 0;
-    const float* wr = w2 + (long)c * SQ;
-    const float* hr = hidden + b * SQ;
-    float a[4] = {0.f, 0.f, 0.f, 0.f};
-    int j = sub;
-    for (; j + 3 * G < SQ; j += 4 * G) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) a[u] = fmaf(wr[j + u * G], hr[j + u * G], a[u]);
-    }
-    for (; j < SQ; j += G) a[0] = fmaf(wr[j], hr[j], a[0]);
-    float acc = (a[0] + a[1]) + (a[2] + a[3]);
-    for (int o = 1; o < G; o <<= 1) acc += __shfl_xor(acc, o, 64);
-    if (!ok) return;
-    const float g = 1.f / (1.f + __expf(-(acc + b2[c])));
-    floatx4 v = *(floatx4*)(y + e);
-    v *= g;
-    *(floatx4*)(y + e) = v;
 }
 
 int check(const DWParams& p, int K, const char* what) {
@@ -587,9 +295,36 @@ int lds_planes(int out_px) {     // planes a workgroup stages per round: ~256 ou
     int P = 256 / (out_px > 0 ? out_px : 1);
     return P < 1 ? 1 : (P > 64 ? 64 : P);
 }
-int grid_for(long n) {
-    const long b = (n + 255) / 256;
-    return (int)(b < 8192 ? (b > 0 ? b : 1) : 8192);
+// Geometry of a staged launch and its dynamic LDS bytes.  Forward placement: x at (pad_t, pad_l) of the padded plane, outputs step by the
+// stride.  Data-gradient placement (dgrad): dy zero-upsampled at (K-1 + oy s, K-1 + ox s), dx steps by one and its taps walk backwards.
+DWLds dw_geometry(const DWParams& p, int K, bool dgrad, size_t& lds) {
+    const int s = p.stride;
+    DWLds q;
+    q.w = p.w; q.out = p.out; q.planes = (long)p.B * p.C; q.C = p.C;
+    if (!dgrad) {
+        q.src = p.x; q.SH = p.H; q.SW = p.W; q.OUTH = p.OH; q.OUTW = p.OW;
+        q.PH = (p.OH - 1) * s + K; q.PW = (p.OW - 1) * s + K;
+        q.ss = 1; q.soy = p.pad_t; q.sox = p.pad_l; q.os = s; q.by = 0; q.bx = 0;
+    } else {
+        q.src = p.dy; q.SH = p.OH; q.SW = p.OW; q.OUTH = p.H; q.OUTW = p.W;
+        // (rows / columns of x that no output covers -- possible at stride 2 -- read the zero slack and get dx = 0)
+        q.PH = (p.OH - 1) * s + 2 * (K - 1) + s + 1; q.PW = (p.OW - 1) * s + 2 * (K - 1) + s + 1;
+        q.ss = s; q.soy = K - 1; q.sox = K - 1; q.os = 1; q.by = p.pad_t + K - 1; q.bx = p.pad_l + K - 1;
+    }
+    q.P = lds_planes(q.OUTH * q.OUTW);
+    lds = (size_t)q.P * (q.PH * q.PW + K * K) * 4;
+    return q;
+}
+dim3 lds_grid(const DWLds& q) { return dim3((unsigned)((q.planes + q.P - 1) / q.P)); }
+// One 256-thread launch of the K = 3 or K = 5 instantiation of a kernel (check() has seen to K); pick(integral_constant<int, K>) names it.
+template <class Pick, class... A>
+int launch_k(int K, Pick pick, dim3 grid, size_t lds, void* stream, const A&... a) {
+    return with_const<2>(K == 5, [&](auto k5) -> int {
+        const auto kernel = pick(std::integral_constant<int, 3 + 2 * decltype(k5)::value>{});
+        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, (hipStream_t)stream, a...);
+        SRBH_HIP(hipGetLastError());
+        return SRBH_OK;
+    });
 }
 }  // namespace
 
@@ -598,45 +333,17 @@ extern "C" int srbh_dwconv_fwd(const float* x, const float* w, float* y, int B, 
     SRBH_REQUIRE(x && w && y, "srbh_dwconv_fwd: null pointer");
     DWParams p{x, w, nullptr, y, B, C, H, W, OH, OW, stride, pad_t, pad_l};
     if (int rc = check(p, K, "srbh_dwconv_fwd")) return rc;
-    {
-        DWLds q;
-        q.src = x; q.w = w; q.out = y; q.planes = (long)B * C; q.C = C; q.SH = H; q.SW = W; q.OUTH = OH; q.OUTW = OW;
-        q.PH = (OH - 1) * stride + K; q.PW = (OW - 1) * stride + K; q.ss = 1; q.soy = pad_t; q.sox = pad_l; q.os = stride; q.by = 0; q.bx = 0;
-        q.P = lds_planes(OH * OW);
-        const size_t lds = (size_t)q.P * (q.PH * q.PW + K * K) * 4;
-        if (lds <= DW_LDS_MAX && DW_LDS_FORMS) {
-            const dim3 grid((unsigned)((q.planes + q.P - 1) / q.P));
-            if (K == 3) hipLaunchKernelGGL((dw_lds_kernel<3, 0>), grid, dim3(256), lds, (hipStream_t)stream, q);
-            else hipLaunchKernelGGL((dw_lds_kernel<5, 0>), grid, dim3(256), lds, (hipStream_t)stream, q);
-            SRBH_HIP(hipGetLastError());
-            return SRBH_OK;
-        }
-    }
-    const int g = grid_for((long)B * C * OH * OW);
-    if (K == 3)
-        hipLaunchKernelGGL(dw_fwd_kernel<3>, dim3(g), dim3(256), 0, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL(dw_fwd_kernel<5>, dim3(g), dim3(256), 0, (hipStream_t)stream, p);
-    SRBH_HIP(hipGetLastError());
-    return SRBH_OK;
-}
-
-static bool dw_eval_geometry(DWLds& q, int B, int C, int H, int W, int K, int stride, int pad_t, int pad_l, int OH, int OW, size_t& lds, int& G) {
-    q.planes = (long)B * C; q.C = C; q.SH = H; q.SW = W; q.OUTH = OH; q.OUTW = OW;
-    q.PH = (OH - 1) * stride + K; q.PW = (OW - 1) * stride + K; q.ss = 1; q.soy = pad_t; q.sox = pad_l; q.os = stride; q.by = 0; q.bx = 0;
-    q.P = lds_planes(OH * OW);
-    lds = (size_t)q.P * (q.PH * q.PW + K * K) * 4;
-    G = 1;
-    while (G < OH * OW && G < 256) G <<= 1;
-    return lds <= DW_LDS_MAX && (K == 3 || K == 5);
+    size_t lds;
+    const DWLds q = dw_geometry(p, K, false, lds);
+    if (lds <= DW_LDS_MAX && DW_LDS_FORMS) return launch_k(K, [](auto k) { return dw_lds_kernel<decltype(k)::value, 0>; }, lds_grid(q), lds, stream, q);
+    return launch_k(K, [](auto k) { return dw_fwd_kernel<decltype(k)::value>; }, dim3(grid_for((long)B * C * OH * OW)), 0, stream, p);
 }
 
 extern "C" int srbh_dwconv_eval_supported(int B, int C, int H, int W, int K, int stride, int pad_t, int pad_l, int OH, int OW) {
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0 || (stride != 1 && stride != 2)) return 0;
-    DWLds q;
     size_t lds;
-    int G;
-    return dw_eval_geometry(q, B, C, H, W, K, stride, pad_t, pad_l, OH, OW, lds, G) ? 1 : 0;
+    dw_geometry(DWParams{nullptr, nullptr, nullptr, nullptr, B, C, H, W, OH, OW, stride, pad_t, pad_l}, K, false, lds);
+    return lds <= DW_LDS_MAX && (K == 3 || K == 5);
 }
 
 extern "C" int srbh_dwconv_eval_fwd(const float* x, const float* w, const float* pre_scale, const float* pre_shift, const float* scale,
@@ -646,27 +353,12 @@ extern "C" int srbh_dwconv_eval_fwd(const float* x, const float* w, const float*
     SRBH_REQUIRE((pre_scale == nullptr) == (pre_shift == nullptr), "srbh_dwconv_eval_fwd: pre_scale and pre_shift go together");
     DWParams p{x, w, nullptr, y, B, C, H, W, OH, OW, stride, pad_t, pad_l};
     if (int rc = check(p, K, "srbh_dwconv_eval_fwd")) return rc;
-    DWLds q;
     size_t lds;
+    const DWLds q = dw_geometry(p, K, false, lds);
+    SRBH_REQUIRE(lds <= DW_LDS_MAX, "srbh_dwconv_eval_fwd: plane too large for the LDS-staged form (srbh_dwconv_eval_supported)");
     DWEval e{pre_scale, pre_shift, scale, shift, pooled, 1};
-    SRBH_REQUIRE(dw_eval_geometry(q, B, C, H, W, K, stride, pad_t, pad_l, OH, OW, lds, e.G), "srbh_dwconv_eval_fwd: plane too large for the "
-                 "LDS-staged form (srbh_dwconv_eval_supported)");
-    q.src = x; q.w = w; q.out = y;
-    const dim3 grid((unsigned)((q.planes + q.P - 1) / q.P));
-    if (K == 3) hipLaunchKernelGGL(dw_lds_eval_kernel<3>, grid, dim3(256), lds, (hipStream_t)stream, q, e);
-    else hipLaunchKernelGGL(dw_lds_eval_kernel<5>, grid, dim3(256), lds, (hipStream_t)stream, q, e);
-    SRBH_HIP(hipGetLastError());
-    return SRBH_OK;
-}
-
-extern "C" int srbh_se_gate(const float* hidden, const float* w2, const float* b2, float* gate, int B, int C, int SQ, void* stream) {
-    SRBH_REQUIRE(hidden && w2 && b2 && gate, "srbh_se_gate: null pointer");
-    SRBH_REQUIRE(B > 0 && C > 0 && SQ > 0, "srbh_se_gate: bad shape");
-    SRBH_REQUIRE((B + SE_GATE_IB - 1) / SE_GATE_IB <= 65535, "srbh_se_gate: batch too large");
-    hipLaunchKernelGGL(se_gate_kernel, dim3((unsigned)((C + 15) / 16), (unsigned)((B + SE_GATE_IB - 1) / SE_GATE_IB)), dim3(256), 0,
-                       (hipStream_t)stream, hidden, w2, b2, gate, B, C, SQ);
-    SRBH_HIP(hipGetLastError());
-    return SRBH_OK;
+    while (e.G < OH * OW && e.G < 256) e.G <<= 1;
+    return launch_k(K, [](auto k) { return dw_lds_eval_kernel<decltype(k)::value>; }, lds_grid(q), lds, stream, q, e);
 }
 
 extern "C" int srbh_dwconv_bwd_data(const float* dy, const float* w, float* dx, int B, int C, int H, int W, int K, int stride,
@@ -674,29 +366,11 @@ extern "C" int srbh_dwconv_bwd_data(const float* dy, const float* w, float* dx, 
     SRBH_REQUIRE(dy && w && dx, "srbh_dwconv_bwd_data: null pointer");
     DWParams p{nullptr, w, dy, dx, B, C, H, W, OH, OW, stride, pad_t, pad_l};
     if (int rc = check(p, K, "srbh_dwconv_bwd_data")) return rc;
-    {
-        DWLds q;
-        q.src = dy; q.w = w; q.out = dx; q.planes = (long)B * C; q.C = C; q.SH = OH; q.SW = OW; q.OUTH = H; q.OUTW = W;
-        // (rows / columns of x that no output covers -- possible at stride 2 -- read the zero slack and get dx = 0)
-        q.PH = (OH - 1) * stride + 2 * (K - 1) + stride + 1; q.PW = (OW - 1) * stride + 2 * (K - 1) + stride + 1;
-        q.ss = stride; q.soy = K - 1; q.sox = K - 1; q.os = 1; q.by = pad_t + K - 1; q.bx = pad_l + K - 1;
-        q.P = lds_planes(H * W);
-        const size_t lds = (size_t)q.P * (q.PH * q.PW + K * K) * 4;
-        if (lds <= DW_LDS_MAX && DW_LDS_FORMS && H - 1 + pad_t + K - 1 < q.PH && W - 1 + pad_l + K - 1 < q.PW) {
-            const dim3 grid((unsigned)((q.planes + q.P - 1) / q.P));
-            if (K == 3) hipLaunchKernelGGL((dw_lds_kernel<3, 1>), grid, dim3(256), lds, (hipStream_t)stream, q);
-            else hipLaunchKernelGGL((dw_lds_kernel<5, 1>), grid, dim3(256), lds, (hipStream_t)stream, q);
-            SRBH_HIP(hipGetLastError());
-            return SRBH_OK;
-        }
-    }
-    const int g = grid_for((long)B * C * H * W);
-    if (K == 3)
-        hipLaunchKernelGGL(dw_bwd_data_kernel<3>, dim3(g), dim3(256), 0, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL(dw_bwd_data_kernel<5>, dim3(g), dim3(256), 0, (hipStream_t)stream, p);
-    SRBH_HIP(hipGetLastError());
-    return SRBH_OK;
+    size_t lds;
+    const DWLds q = dw_geometry(p, K, true, lds);
+    if (lds <= DW_LDS_MAX && DW_LDS_FORMS && H - 1 + pad_t + K - 1 < q.PH && W - 1 + pad_l + K - 1 < q.PW)
+        return launch_k(K, [](auto k) { return dw_lds_kernel<decltype(k)::value, 1>; }, lds_grid(q), lds, stream, q);
+    return launch_k(K, [](auto k) { return dw_bwd_data_kernel<decltype(k)::value>; }, dim3(grid_for((long)B * C * H * W)), 0, stream, p);
 }
 
 extern "C" int srbh_dwconv_bwd_weight_splits(int B, int C) {
@@ -715,102 +389,12 @@ extern "C" int srbh_dwconv_bwd_weight(const float* x, const float* dy, float* dw
     const size_t lds = (size_t)P * (PH * PW + OH * OW) * 4;
     float* const part = splits == 1 ? dw : ws;                       // (one slice: its sums ARE the gradient, no reduce launch)
     // (the staged form pays for 5x5 and for small planes; a 3x3 over >= 256-pixel planes is as fast from L1: measured per shape)
-    if (lds <= DW_LDS_MAX && DW_LDS_FORMS && (K == 5 || OH * OW < 256)) {
-        if (K == 3) hipLaunchKernelGGL(dw_lds_wgrad_kernel<3>, dim3(C, splits), dim3(256), lds, (hipStream_t)stream, p, part, splits, PH, PW, P);
-        else hipLaunchKernelGGL(dw_lds_wgrad_kernel<5>, dim3(C, splits), dim3(256), lds, (hipStream_t)stream, p, part, splits, PH, PW, P);
-    } else if (K == 3)
-        hipLaunchKernelGGL(dw_bwd_weight_kernel<3>, dim3(C, splits), dim3(256), 0, (hipStream_t)stream, p, part, splits);
-    else
-        hipLaunchKernelGGL(dw_bwd_weight_kernel<5>, dim3(C, splits), dim3(256), 0, (hipStream_t)stream, p, part, splits);
-    SRBH_HIP(hipGetLastError());
-    if (splits == 1) return SRBH_OK;
+    const int rc = lds <= DW_LDS_MAX && DW_LDS_FORMS && (K == 5 || OH * OW < 256)
+                       ? launch_k(K, [](auto k) { return dw_lds_wgrad_kernel<decltype(k)::value>; }, dim3(C, splits), lds, stream, p, part, splits, PH, PW, P)
+                       : launch_k(K, [](auto k) { return dw_bwd_weight_kernel<decltype(k)::value>; }, dim3(C, splits), 0, stream, p, part, splits);
+    if (rc || splits == 1) return rc;
     const int n = C * K * K;
     hipLaunchKernelGGL(dw_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, ws, dw, n, splits);
-    SRBH_HIP(hipGetLastError());
-    return SRBH_OK;
-}
-
-static int affine_act_impl(const float* x, const float* scale, const float* shift, const float* res, float* y, int B, int C, int HW,
-                           int act, void* stream) {
-    SRBH_REQUIRE(x && scale && shift && y, "srbh_affine_act_nchw: null pointer");
-    SRBH_REQUIRE(B > 0 && C > 0 && HW > 0 && act >= 0 && act <= 2, "srbh_affine_act_nchw: bad arguments");
-    const long planes = (long)B * C;
-    const bool v4 = (HW % 4 == 0) && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)res) % 16 == 0);
-    const int g = grid_for(planes * (v4 ? HW / 4 : HW));
-    if (v4)
-        hipLaunchKernelGGL(affine_act_nchw_kernel<4>, dim3(g), dim3(256), 0, (hipStream_t)stream, x, scale, shift, res, y, planes, C, HW, act);
-    else
-        hipLaunchKernelGGL(affine_act_nchw_kernel<1>, dim3(g), dim3(256), 0, (hipStream_t)stream, x, scale, shift, res, y, planes, C, HW, act);
-    SRBH_HIP(hipGetLastError());
-    return SRBH_OK;
-}
-
-// (56 / 64 output channels -- the stems of efficientnet-b6 / b7 -- would need a second accumulator pass: one thread holding 64 accumulators spills)
-extern "C" int srbh_stem_conv_eval_supported(int Cin, int Cout, int K) { return K == 3 && Cin > 0 && Cin <= 16 && (Cout == 32 || Cout == 40 || Cout == 48); }
-
-/* act(conv3x3(x, w, stride, static padding top = pt / left = pl, zeros beyond) * scale[c] + shift[c]) on NCHW fp32; w: OIHW; act 0 none / 1 SiLU / 2 ReLU */
-extern "C" int srbh_stem_conv_eval(const float* x, const float* w, const float* scale, const float* shift, float* y, int B, int Cin, int H, int W,
-                                   int Cout, int stride, int pt, int pl, int OH, int OW, int act, void* stream) {
-    SRBH_REQUIRE(x && w && scale && shift && y, "srbh_stem_conv_eval: null pointer");
-    SRBH_REQUIRE(B > 0 && H > 0 && W > 0 && OH > 0 && OW > 0 && stride >= 1 && pt >= 0 && pl >= 0 && act >= 0 && act <= 2 && srbh_stem_conv_eval_supported(Cin, Cout, 3),
-                 "srbh_stem_conv_eval: bad arguments (3x3, Cin <= 16, Cout in {32, 40, 48})");
-    const long total = (long)B * OH * OW;
-    const dim3 grid((unsigned)((total + 255) / 256));
-    const size_t lds = (size_t)Cin * 9 * Cout * sizeof(float);
-    hipStream_t st = (hipStream_t)stream;
-#define SRBH_STEM(C4_) hipLaunchKernelGGL((stem_conv_eval_kernel<C4_>), grid, dim3(256), lds, st, x, w, scale, shift, y, B, Cin, H, W, stride, pt, pl, OH, OW, act)
-    switch (Cout) { case 32: SRBH_STEM(8); break; case 40: SRBH_STEM(10); break; default: SRBH_STEM(12); }
-#undef SRBH_STEM
-    SRBH_HIP(hipGetLastError());
-    return SRBH_OK;
-}
-
-extern "C" int srbh_affine_act_nchw(const float* x, const float* scale, const float* shift, float* y, int B, int C, int HW, int act,
-                                    void* stream) {
-    return affine_act_impl(x, scale, shift, nullptr, y, B, C, HW, act, stream);
-}
-
-extern "C" int srbh_affine_act_add_nchw(const float* x, const float* scale, const float* shift, const float* res, float* y, int B, int C,
-                                        int HW, int act, void* stream) {
-    SRBH_REQUIRE(res, "srbh_affine_act_add_nchw: null residual");
-    return affine_act_impl(x, scale, shift, res, y, B, C, HW, act, stream);
-}
-
-extern "C" int srbh_affine_act_pool_nchw(const float* x, const float* scale, const float* shift, float* y, float* pooled, int B, int C,
-                                         int HW, int act, void* stream) {
-    SRBH_REQUIRE(x && scale && shift && y && pooled, "srbh_affine_act_pool_nchw: null pointer");
-    SRBH_REQUIRE(B > 0 && C > 0 && HW > 0 && act >= 0 && act <= 2, "srbh_affine_act_pool_nchw: bad arguments");
-    const long planes = (long)B * C;
-    if (HW < 64 && (HW & (HW - 1)) == 0)
-        hipLaunchKernelGGL(affine_act_pool_small_kernel, dim3((unsigned)((planes * HW + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, scale,
-                           shift, y, pooled, planes, C, HW, act);
-    else
-        hipLaunchKernelGGL(affine_act_pool_kernel, dim3((unsigned)((planes + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, scale, shift, y,
-                           pooled, planes, C, HW, act);
-    SRBH_HIP(hipGetLastError());
-    return SRBH_OK;
-}
-
-extern "C" int srbh_se_hidden(const float* pooled, const float* w1, const float* b1, float* hidden, int B, int C, int SQ,
-                              void* stream) {
-    SRBH_REQUIRE(pooled && w1 && b1 && hidden, "srbh_se_hidden: null pointer");
-    SRBH_REQUIRE(B > 0 && C > 0 && SQ > 0 && SQ <= 65535 * 4, "srbh_se_hidden: bad shape");
-    hipLaunchKernelGGL(se_hidden_kernel, dim3(B, (SQ + 3) / 4), dim3(256), 0, (hipStream_t)stream, pooled, w1, b1, hidden, C, SQ);
-    SRBH_HIP(hipGetLastError());
-    return SRBH_OK;
-}
-
-extern "C" int srbh_se_gate_scale(float* y, const float* hidden, const float* w2, const float* b2, int B, int C, int SQ, int HW,
-                                  void* stream) {
-    SRBH_REQUIRE(y && hidden && w2 && b2, "srbh_se_gate_scale: null pointer");
-    SRBH_REQUIRE(B > 0 && C > 0 && SQ > 0 && HW > 0, "srbh_se_gate_scale: bad shape");
-    const long planes = (long)B * C;
-    if ((HW == 4 || HW == 16 || HW == 64 || HW == 256) && ((uintptr_t)y & 15) == 0)
-        hipLaunchKernelGGL(se_gate_scale_quad_kernel, dim3((unsigned)((planes * HW + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, y, hidden,
-                           w2, b2, planes, C, SQ, HW);
-    else
-        hipLaunchKernelGGL(se_gate_scale_kernel, dim3((unsigned)((planes + 3) / 4)), dim3(256), 0, (hipStream_t)stream, y, hidden, w2, b2,
-                           planes, C, SQ, HW);
     SRBH_HIP(hipGetLastError());
     return SRBH_OK;
 }

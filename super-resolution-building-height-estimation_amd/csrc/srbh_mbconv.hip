@@ -478,7 +478,7 @@ __global__ __launch_bounds__(256) void se_bwd_params_kernel(const GemmTN g0, con
     }
 }
 
-// training forms of the two inference squeeze-excite kernels (srbh_dwconv.hip): they also keep what the backward needs
+// training forms of the two inference squeeze-excite kernels (srbh_enc_eval.hip): they also keep what the backward needs
 __global__ __launch_bounds__(256) void se_hidden_train_kernel(const float* __restrict__ pooled, const float* __restrict__ w1,
                                                              const float* __restrict__ b1, float* __restrict__ hidden,
                                                              float* __restrict__ hidden_pre, int C, int SQ) {

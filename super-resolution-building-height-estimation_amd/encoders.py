@@ -234,7 +234,7 @@ MBCONV_EVAL = __import__("os").environ.get("SRBH_MBCONV_EVAL", "1") == "1"
 def bn_act(bn, x, act=None, res=None, drop=None):
     """BatchNorm2d followed by an activation [, the drop-connect factor `drop` (B,) and the skip connection `res`].  Inference on
     the device: ONE libsrbh pass y = act(x * scale + shift) with the running statistics folded into (scale, shift)
-    (csrc/srbh_dwconv.hip) -- MIOpen's inference-BatchNorm kernel costs ~39 us per call whatever the size, 8.6 % of the
+    (csrc/srbh_enc_eval.hip) -- MIOpen's inference-BatchNorm kernel costs ~39 us per call whatever the size, 8.6 % of the
     tiled-inference path.  Training on the device, planes below 32x32: one libsrbh launch forward and one backward
     (mbconv_autograd.bn_act_train).  Otherwise (CPU, large planes, SyncBatchNorm): the stock ops."""
     if x.is_cuda and bn.training:
@@ -328,7 +328,7 @@ def _stem_eval(conv, bn, x):
 
 def bn_swish_se(bn, x, se_reduce, se_expand):
     """MBConv middle at inference: swish(bn(x)) followed by squeeze-and-excitation, as THREE libsrbh launches
-    (csrc/srbh_dwconv.hip) instead of ~11 stock-op ones per block: the encoder is bound by its launch count."""
+    (csrc/srbh_enc_eval.hip) instead of ~11 stock-op ones per block: the encoder is bound by its launch count."""
     from . import _lib
     L = _lib.lib()
     scale, shift = _bn_affine(bn, x.device)

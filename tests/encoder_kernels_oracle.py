@@ -1,4 +1,4 @@
-"""float64 stock-op restatement of the encoder's small kernels (csrc/srbh_dwconv.hip, srbh_bn_eval_scale_shift)  --  TEST INFRASTRUCTURE ONLY.
+"""float64 stock-op restatement of the encoder's small kernels (csrc/srbh_dwconv.hip, csrc/srbh_enc_eval.hip, srbh_bn_eval_scale_shift)  --  TEST INFRASTRUCTURE ONLY.
 
 One plain torch function per C-ABI entry point, evaluated in float64 on the CPU whatever the inputs' type, plus the launch
 arithmetic of the depthwise dispatcher restated in Python (batch slices of the weight gradient, LDS byte counts of the staged

@@ -1,4 +1,4 @@
-"""CPU: tests/encoder_kernels_oracle.py itself -- the float64 functions the GPU tests of csrc/srbh_dwconv.hip compare against equal the
+"""CPU: tests/encoder_kernels_oracle.py itself -- the float64 functions the GPU tests of csrc/srbh_dwconv.hip and csrc/srbh_enc_eval.hip compare against equal the
 stock float64 module chain of encoders.MBConvBlock in eval mode, the depthwise reference equals the padded grouped conv under the
 encoder's TF-"same" padding, and the shape lists of tests/test_gpu_dwconv.py have the slice / round / LDS-limit properties they were
 chosen for.  No kernel is launched here (the kernels: tests/test_gpu_encoder_kernels.py, tests/test_gpu_dwconv.py)."""

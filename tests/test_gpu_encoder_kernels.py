@@ -1,4 +1,4 @@
-"""The inference BatchNorm, affine + activation and squeeze-and-excitation kernels of csrc/srbh_dwconv.hip (and srbh_bn_eval_scale_shift),
+"""The inference BatchNorm, affine + activation and squeeze-and-excitation kernels of csrc/srbh_enc_eval.hip (and srbh_bn_eval_scale_shift),
 each entry point on its own through the C ABI against the float64 functions of tests/encoder_kernels_oracle.py, at the shapes where
 their dispatch changes form: the float4 and the scalar affine pass (plane sizes that are no multiple of 4, pointers that are only
 4-byte aligned, y aliasing x, more work items than one grid stride), the wave-per-plane and the small-plane pooling kernels with ragged
