@@ -737,7 +737,20 @@ int srbh_pwconv_wgrad_plan(int B, int Cin, int Cout, int HW, int* vec, int* kw, 
  *   round(softmax*255) (both round-half-even, uint16 range) into uint32 mosaics [H][W], [C][H][W] and 1 into the
  *   weight mosaic, with atomics.  finalize: build class = argmax of the class sums (mod 2^16), height =
  *   round(sum/weight) where weight (mod 2^8) > 0 -- bit-identical to the reference's uint16/uint8 numpy arrays for any
- *   tile order or sharding (mosaics of different ranks add). */
+ *   tile order or sharding (mosaics of different ranks add).
+ * The contract in full (tests/test_gpu_mosaic_forms.py pins every line of it):
+ *   accumulate  1 <= C <= 16 (the exponentials of a pixel are kept in registers), B, th, tw, H, W > 0, no null pointer; anything else
+ *               is refused with nothing launched.  pos is in MOSAIC PIXELS.  Pixel (x, y) of tile b is added at (xoff + x, yoff + y) iff
+ *               x < xcount, y < ycount and the target lies inside [0, W) x [0, H): counts beyond the tile are bounded by the tile,
+ *               counts <= 0 and pixels off the city add nothing (the window arithmetic is 64-bit: no content of pos overflows it).
+ *               The height quantum is rintf(fl32(max(h, 0) * 10)) mod 2^16 (h = -0.0 counts as 0), the class quantum
+ *               rintf(e_c / s * 255) with e_c = expf(fl32(z_c - max z)), s = the fp32 sum of e in class order 0 .. C - 1.  The
+ *               mosaics are added to, never cleared: whatever they hold (high bits included) stays in the sums.
+ *   finalize    C >= 1 with NO upper limit (one pass over the class sums, nothing kept per class), H, W > 0, no null pointer.  Only
+ *               res_height & 0xffff, res_build & 0xffff and res_weight & 0xff are read: the higher bits of the accumulators never
+ *               reach an output.  build_out = the FIRST class holding the largest masked sum; height_out = rint(h16 / w8) in double
+ *               (half to even) where w8 > 0, else h16 itself -- so a pixel covered by 256 tiles keeps its undivided (wrapped) sum, as
+ *               the reference's uint8 weight does.  The three accumulators are not written. */
 int srbh_mosaic_accumulate(const float* height, const float* build, int C, int B, int th, int tw, const int* pos,
                            unsigned* res_height, unsigned* res_build, unsigned* res_weight, int H, int W, void* stream);
 int srbh_mosaic_finalize(const unsigned* res_height, const unsigned* res_build, const unsigned* res_weight, int C, int H,
@@ -747,7 +760,15 @@ int srbh_mosaic_finalize(const unsigned* res_height, const unsigned* res_build, 
  * label_prep: height uint8 [B][H][W] -> build (int64 class = buildhir_lut[height]), height as float,
  *   weight = class_weight[build], and per 4x4 cell height_aggre = aggregate_torch(height, 0.25),
  *   weight_aggre = class_weight[buildhir_lut[(long)height_aggre]]  ([B][H/4][W/4]).
- * normalize_clamp: dst = clip((src - mins[c]) / ranges[c], lo, hi) on NCHW fp32 (clip only when clamp != 0). */
+ * normalize_clamp: dst = clip((src - mins[c]) / ranges[c], lo, hi) on NCHW fp32 (clip only when clamp != 0).
+ * The contract in full (tests/test_gpu_loader_forms.py pins every line of it):
+ *   label_prep       B, H, W > 0, H and W multiples of 4, no null pointer, `height` 4-byte aligned (it is read four labels at a time);
+ *                    anything else is refused with nothing launched.  Every output is exact: a cell's sum of 16 uint8 labels is an
+ *                    integer <= 4080, exact in fp32 in any order, and the divisor fl32(16 + 1e-10) IS 16, so height_aggre is the exact
+ *                    quotient sum / 16 and (long)height_aggre its floor; class weights are copied bit for bit.
+ *   normalize_clamp  every dimension > 0, no null pointer.  Two correctly rounded fp32 operations, so dst equals the IEEE value bit for
+ *                    bit.  The clip is `v < lo ? lo : (v > hi ? hi : v)`, as img[img < lo] = lo; img[img > hi] = hi: NaN (0 / 0 of a band
+ *                    with range 0, or NaN in src) stays NaN with or without the clip, -0.0 stays -0.0 under lo = 0, +-inf become hi / lo. */
 int srbh_label_prep(const unsigned char* height, int B, int H, int W, const unsigned char* buildhir_lut,
                     const float* class_weight, long long* build, float* height_f, float* weight, float* height_aggre,
                     float* weight_aggre, void* stream);

@@ -30,7 +30,7 @@ def label_prep(height_u8, hir, heightweight):
     build_aggre = lut[height_aggre.long().numpy()]                # :389
     weight_aggre = heightweight[build_aggre]                      # :390
     return (height, height_aggre, torch.from_numpy(build).long(), torch.from_numpy(weight).float(),
-            torch.from_numpy(weight_aggre).float())
+            torch.from_numpy(np.asarray(weight_aggre)).float())      # (asarray: a 4 x 4 label gives a 0-d aggregate)
 
 
 def normalize(img_chw, mins, maxs, datarange=(0, 1)):

@@ -315,6 +315,7 @@ extern "C" int srbh_label_prep(const unsigned char* height, int B, int H, int W,
     SRBH_REQUIRE(height && buildhir_lut && class_weight && build && height_f && weight && height_aggre && weight_aggre,
                  "srbh_label_prep: null pointer");
     SRBH_REQUIRE(B > 0 && H > 0 && W > 0 && H % 4 == 0 && W % 4 == 0, "srbh_label_prep: H, W must be multiples of 4");
+    SRBH_REQUIRE(((uintptr_t)height & 3) == 0, "srbh_label_prep: height must be 4-byte aligned");      // read as uchar4
     long total = (long)B * (H / 4) * (W / 4);
     hipLaunchKernelGGL(label_prep_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, height, B, H, W,
                        buildhir_lut, class_weight, build, height_f, weight, height_aggre, weight_aggre);

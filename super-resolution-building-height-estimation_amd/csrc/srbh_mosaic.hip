@@ -33,12 +33,12 @@ __global__ void mosaic_accumulate_kernel(const float* __restrict__ height, const
     const int b = r / th;
     const int xoff = pos[b * 4 + 0], yoff = pos[b * 4 + 1], xcount = pos[b * 4 + 2], ycount = pos[b * 4 + 3];
     if (x >= xcount || y >= ycount) return;
-    const int X = xoff + x, Y = yoff + y;
-    if (X < 0 || X >= W || Y < 0 || Y >= H) return;   // (the reference would raise on such a tile)
+    const long X = (long)xoff + x, Y = (long)yoff + y;   // 64-bit as grid_tiles_kernel: no content of pos overflows the window arithmetic
+    if (X < 0 || X >= W || Y < 0 || Y >= H) return;      // (the reference would raise on such a tile)
     float hv = height[idx];
     hv = hv < 0.f ? 0.f : hv;                                            // ypred[ypred<0] = 0
     const unsigned hq = ((unsigned)rintf(hv * 10.f)) & 0xffffu;          // np.round(.*10).astype(uint16)
-    const long o = (long)Y * W + X;
+    const long o = Y * W + X;
     atomicAdd(res_h + o, hq);
     atomicAdd(res_w + o, 1u);
     const float* lg = build + idx * C;

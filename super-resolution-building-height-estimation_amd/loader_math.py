@@ -55,6 +55,8 @@ class LabelPrep:
         if not (height_u8.is_cuda and height_u8.dtype == torch.uint8 and height_u8.dim() == 3):
             raise RuntimeError("LabelPrep (libsrbh): expects a (B,H,W) uint8 device tensor")
         h = height_u8.contiguous()
+        if h.data_ptr() % 4:          # a contiguous view may start at any byte; the kernel reads four labels at a time
+            h = h.clone()
         B, Hh, Ww = h.shape
         dev = h.device
         build = torch.empty((B, Hh, Ww), dtype=torch.int64, device=dev)

@@ -25,12 +25,13 @@ class Mosaic:
         if not (ypred.is_cuda and build_pred.is_cuda):
             raise RuntimeError("Mosaic.add (libsrbh): device tensors only (no CPU fallback)")
         n, _, th, tw = ypred.shape
+        if n == 0:                   # an empty batch adds nothing (srbh_mosaic_accumulate refuses B = 0)
+            return
         hv = ypred.detach().float().contiguous()
         bl = H.to_nhwc(build_pred.detach().float())
         pos_h = torch.as_tensor(posall, dtype=torch.int32).reshape(n, 4) * 4
-        if n:
-            self._rows[0] = min(self._rows[0], max(0, int(pos_h[:, 1].min())))
-            self._rows[1] = max(self._rows[1], min(self.H, int((pos_h[:, 1] + pos_h[:, 3]).max())))
+        self._rows[0] = min(self._rows[0], max(0, int(pos_h[:, 1].min())))
+        self._rows[1] = max(self._rows[1], min(self.H, int((pos_h[:, 1] + pos_h[:, 3]).max())))
         pos = pos_h.to(ypred.device).contiguous()
         _lib.check(_lib.lib().srbh_mosaic_accumulate(hv.data_ptr(), bl.data_ptr(), self.C, n, th, tw, pos.data_ptr(),
                                                      self.res_height.data_ptr(), self.res_build.data_ptr(),

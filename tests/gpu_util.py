@@ -117,12 +117,14 @@ def ref_conv64(x, w, b):
 
 # ---- memory contract of one C-ABI call: writes stay inside the outputs, inputs stay as they were -------------------------------------
 SLACK = 64          # floats of NaN on either side of every output (256 bytes of guard for every other element type)
-SENTINEL = {torch.int64: 0x5AA5A55A5AA5A55A, torch.uint8: 0xA5}      # guard pattern of the integer types, which have no NaN
+# guard pattern of the integer types, which have no NaN.  uint32 / uint16 data (the mosaics' accumulators, the finalised height) live in
+# int32 / int16 storage -- torch lacks most ops on the unsigned types -- and are read back as bit patterns through a numpy view
+SENTINEL = {torch.int64: 0x5AA5A55A5AA5A55A, torch.int32: 0x5AA5A55A, torch.int16: 0x5AA5, torch.uint8: 0xA5}
 
 
 class GuardedBuffers:
     """the device buffers of one call: inputs with a clone to compare with afterwards, outputs carved out of guard-filled storage (NaN for
-    the float types, SENTINEL for int64 / uint8).  `offset` counts ELEMENTS of the buffer's dtype past a 16-byte boundary."""
+    the float types, SENTINEL for the integer types).  `offset` counts ELEMENTS of the buffer's dtype past a 16-byte boundary."""
 
     def __init__(self):
         self.inputs, self.outputs, self.before = [], [], {}
@@ -173,5 +175,5 @@ class GuardedBuffers:
             if not written:
                 was = self.before[id(buf)]          # what the output held before the call: its guard pattern, or the `fill`
                 assert bool(self._is_guard(v).all()) if was is None else torch.equal(v, was), "a refused call wrote to an output"
-            elif v.dtype != torch.uint8:      # (a byte may equal its guard by chance)
+            elif v.element_size() > 2:        # (a byte or a 16-bit value may equal its guard by chance)
                 assert not bool(self._is_guard(v).any()), "an output element was left unwritten (or is NaN)"

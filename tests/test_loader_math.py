@@ -24,8 +24,15 @@ def test_hierweight_known_answers(golden_dir):
     assert abs(LM.hierweight(stats, HIR).sum() - 7.0) < 1e-9        # the rescale makes the weights sum to the class count
 
 
+def _bits(t):
+    return t.detach().cpu().contiguous().view(torch.int32)
+
+
 @pytest.mark.gpu
 def test_label_prep_and_normalize_kernels(golden_dir):
+    """every output EQUAL to the oracle: a 4x4 block sum of uint8 labels is an integer <= 4080, exact in fp32 in any order, and the divisor
+    fl32(16 + 1e-10) is 16, so the aggregates carry no sum-order noise; (x - min) / range is two correctly rounded fp32 operations, so the
+    normalised tiles match bit for bit (tests/test_gpu_loader_forms.py holds every form of the two kernels to the same)"""
     from oracle import loader_oracle as LO
     from srbh_amd import loader_math as LM
     g = np.load(os.path.join(golden_dir, "g9_hierweight.npz"))
@@ -40,18 +47,17 @@ def test_label_prep_and_normalize_kernels(golden_dir):
         oh, oha, ob, ow, owa = LO.label_prep(lab[i].numpy(), HIR, hw)
         assert torch.equal(hf[i].cpu(), oh) and torch.equal(build[i].cpu(), ob)
         assert torch.equal(wt[i].cpu(), ow)
-        assert torch.allclose(ha[i].cpu(), oha, rtol=1e-6, atol=1e-6)
-        # class of the aggregated height may flip only where the mean sits on an integer boundary (sum-order noise)
-        assert float((wa[i].cpu() != owa).float().mean()) < 1e-3
+        assert torch.equal(_bits(ha[i]), _bits(oha)) and torch.equal(_bits(wa[i]), _bits(owa))
     img = torch.rand(2, 8, 64, 64, generator=gen) * 3000 - 200
     mins = np.linspace(-100, 50, 8)
     maxs = mins + np.linspace(1500, 2600, 8)
     out = LM.normalize_tiles(img.to("cuda:0"), mins, maxs, (0, 1))
     want = torch.stack([LO.normalize(img[i], mins, maxs, (0, 1)) for i in range(2)])
-    assert torch.allclose(out.cpu(), want, rtol=1e-6, atol=1e-7)
+    assert torch.equal(_bits(out), _bits(want))
     assert float(out.min()) == 0.0 and float(out.max()) == 1.0
     out2 = LM.normalize_tiles(img.to("cuda:0"), mins, maxs, None)     # grid loader: no clip (BH_loader.py:984-986)
     assert float(out2.min()) < 0.0
+    assert torch.equal(_bits(out2), _bits(torch.stack([LO.normalize(img[i], mins, maxs, None) for i in range(2)])))
 
 
 def _g13(golden_dir):
@@ -74,6 +80,11 @@ def test_loader_oracle_matches_reference_dataset_outputs(golden_dir):
 
 @pytest.mark.gpu
 def test_loader_kernels_match_reference_dataset_outputs(golden_dir):
+    """labels, weights and both aggregates EQUAL the reference's outputs.  The normalised tiles equal the oracle bit for bit; against the
+    FIXTURE they keep the fp32-rounding bound, because the fixture itself is not the fp32 chain: the oracle's (x - min) / range in fp32
+    differs from the reference's stored img by one ulp at 52 / 53 / 57 of 2048 elements of the three samples (the reference divides in
+    float64 and rounds once; test_loader_oracle_matches_reference_dataset_outputs holds the oracle to the same bound for that reason)"""
+    from oracle import loader_oracle as LO
     from srbh_amd import loader_math as LM
     g = _g13(golden_dir)
     n = g["s2"].shape[0]
@@ -82,7 +93,8 @@ def test_loader_kernels_match_reference_dataset_outputs(golden_dir):
     prep = LM.LabelPrep(HIR, g["heightweight"], "cuda:0")
     hf, ha, build, wt, wa = prep(torch.from_numpy(g["height_u8"]).to("cuda:0"))
     for i in range(n):
+        assert torch.equal(_bits(img[i]), _bits(LO.normalize(raw[i], g["mins"], g["maxs"], (0, 1))))
         assert torch.allclose(img[i], torch.from_numpy(g[f"img{i}"]), rtol=1e-6, atol=1e-7)
         assert np.array_equal(build[i].cpu().numpy(), g[f"build{i}"]) and np.array_equal(wt[i].cpu().numpy(), g[f"weight{i}"])
-        assert np.allclose(ha[i].cpu().numpy(), g[f"height_aggre{i}"], rtol=1e-6, atol=1e-6)
-        assert float((wa[i].cpu().numpy() != g[f"weight_aggre{i}"]).mean()) < 1e-2
+        assert np.array_equal(ha[i].cpu().numpy(), g[f"height_aggre{i}"].reshape(ha[i].shape))
+        assert np.array_equal(wa[i].cpu().numpy(), g[f"weight_aggre{i}"].reshape(wa[i].shape))
