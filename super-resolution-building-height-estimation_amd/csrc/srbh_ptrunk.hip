@@ -151,13 +151,15 @@ int ptrunk_takes(int num_block, int H, int W, int* takes, int* ncu_out) {
     if (H / TILE_H > ncu) return SRBH_OK;
     constexpr int LDS_B = P_LDS_B;
     SRBH_ONCE_PER_DEVICE({
-        SRBH_HIP(hipFuncSetAttribute((const void*)ptrunk3_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B));
-        SRBH_HIP(hipFuncSetAttribute((const void*)ptrunk3_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B));
-        SRBH_HIP(hipFuncSetAttribute((const void*)ptrunk3_kernel<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B));
-        SRBH_HIP(hipFuncSetAttribute((const void*)ptrunk3_kernel<0, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B));
+        // <PROF, BW, BF, TRAIN>: fp16 inference, its developer timeline, bf16 inference, training forward, training backward
+        SRBH_HIP(hipFuncSetAttribute((const void*)ptrunk3_kernel<0, 0, 0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B));
+        SRBH_HIP(hipFuncSetAttribute((const void*)ptrunk3_kernel<1, 0, 0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B));
+        SRBH_HIP(hipFuncSetAttribute((const void*)ptrunk3_kernel<0, 0, 1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B));
+        SRBH_HIP(hipFuncSetAttribute((const void*)ptrunk3_kernel<0, 0, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B));
+        SRBH_HIP(hipFuncSetAttribute((const void*)ptrunk3_kernel<0, 1, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B));
     });
     int per_cu = 0;
-    SRBH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ptrunk3_kernel<0>, 256, LDS_B));
+    SRBH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ptrunk3_kernel<0, 0, 0, 0>, 256, LDS_B));
     if (per_cu < 1) return SRBH_OK;
     *takes = 1;
     return SRBH_OK;
@@ -239,23 +241,27 @@ int ptrunk_run(const srbh_rrdbnet_desc* d, void* dense0, void* dense1, float* xr
             const char* e = getenv("SRBH_PT_WT");
             pp.force_wt = (e && atoi(e) == 1) ? 1 : 0;
         }
-        if (getenv("SRBH_PT_PROF") && !bf16 && !g_ptrunk_prof)      // (the developer timeline exists for the fp16 form only)
+        const bool timeline = !bf16 && train_stride == 0;      // (the developer timeline exists for the fp16 inference form only)
+        if (getenv("SRBH_PT_PROF") && timeline && !g_ptrunk_prof)
             SRBH_HIP(hipMalloc(&g_ptrunk_prof, (size_t)ncu * MAX_BLOCKS * 15 * 6 * 8));
-        pp.prof = bf16 ? nullptr : g_ptrunk_prof;
+        pp.prof = timeline ? g_ptrunk_prof : nullptr;
         if (g_trunk_timing && b0 == 0) SRBH_HIP(hipEventRecord(g_trunk_ev[0], stream));
         g_trunk_kernel = "ptrunk3_kernel";
+        // (TRAIN = 1 only where the training switches of PParams can be set: the inference forms are compiled without them)
         if (mask)
-            hipLaunchKernelGGL((ptrunk3_kernel<0, 1>), dim3(pp.nblocks), dim3(256), LDS_B, stream, pp);
+            hipLaunchKernelGGL((ptrunk3_kernel<0, 1, 0, 1>), dim3(pp.nblocks), dim3(256), LDS_B, stream, pp);
+        else if (train_stride > 0)
+            hipLaunchKernelGGL((ptrunk3_kernel<0, 0, 0, 1>), dim3(pp.nblocks), dim3(256), LDS_B, stream, pp);
         else if (bf16)
-            hipLaunchKernelGGL((ptrunk3_kernel<0, 0, 1>), dim3(pp.nblocks), dim3(256), LDS_B, stream, pp);
+            hipLaunchKernelGGL((ptrunk3_kernel<0, 0, 1, 0>), dim3(pp.nblocks), dim3(256), LDS_B, stream, pp);
         else if (pp.prof)
-            hipLaunchKernelGGL((ptrunk3_kernel<1>), dim3(pp.nblocks), dim3(256), LDS_B, stream, pp);
+            hipLaunchKernelGGL((ptrunk3_kernel<1, 0, 0, 0>), dim3(pp.nblocks), dim3(256), LDS_B, stream, pp);
         else
-            hipLaunchKernelGGL((ptrunk3_kernel<0>), dim3(pp.nblocks), dim3(256), LDS_B, stream, pp);
+            hipLaunchKernelGGL((ptrunk3_kernel<0, 0, 0, 0>), dim3(pp.nblocks), dim3(256), LDS_B, stream, pp);
         SRBH_HIP(hipGetLastError());
     }
     if (g_trunk_timing) { SRBH_HIP(hipEventRecord(g_trunk_ev[1], stream)); g_trunk_ev_recorded = 1; }
-    if (getenv("SRBH_PT_PROF") && g_ptrunk_prof && !bf16) {   // developer aid: cycles vs wall clock of the real forward
+    if (getenv("SRBH_PT_PROF") && g_ptrunk_prof && !bf16 && train_stride == 0) {   // developer aid: cycles vs wall clock of the real forward
         SRBH_HIP(hipStreamSynchronize(stream));
         const int nblk = (B < imgs_per_launch ? B : imgs_per_launch) * tpi;
         std::vector<unsigned long long> h((size_t)nblk * nl * 6);

@@ -74,11 +74,6 @@
 // Steps of one layer only (the epilogue separates layers).
 #define P3_PREREAD 1
 #endif
-#ifndef P3_TRAIN
-// 1: the kernel also runs the SR-stage TRAINING forward (PParams.dense_stride / keep_all / out_pixel: one dense buffer per RDB, whole planes,
-// fp32 output in pixel order); 0 compiles those run-time switches out (A/B aid: what they cost the inference launch)
-#define P3_TRAIN 1
-#endif
 #ifndef P3_PRE_AT
 #define P3_PRE_AT 2
 #endif
@@ -131,41 +126,23 @@
 // capped clock rises by ~8 % (profiles/r08a_mfma_ceiling_bf16.txt).  The fp32 RRDB stream stays fp32, and the LAST RDB rounds the trunk's
 // output planes to fp16 as the fp16 form does (`f16out`): conv_body and the up-sampler tail read fp16.  Training forward and backward
 // never run this form.
-template <int PROF, int BW = 0, int BF = 0>
+// TRAIN = 1: the kernel also runs the SR-stage TRAINING forward and backward (PParams.dense_stride / keep_all / out_pixel: one dense buffer per
+// RDB, whole planes, fp32 output in pixel order); the inference forms (TRAIN = 0) carry none of those run-time switches.
+// The RDB loop is PEELED: `rdb_body` is one generic body compiled twice, the loop form (every RDB but the last: conv5's epilogue keeps only
+// the halo rows of the new x, rounds to the trunk's operand format, prefetches the next conv1's weights and ends in the seam) and the
+// last-RDB form behind the loop (no seam, the trunk's output planes whole, fp16 in the bf16 form, the training forward's pixel-order
+// output).  What used to be run-time flags that change once per launch are compile-time properties of the two forms; behind the peeled
+// body nothing is live, so the two epilogue bodies never meet in phis (two epilogue bodies inside ONE loop body once cost 184 spills).
+template <int PROF, int BW, int BF, int TRAIN>
 __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l31 = lane & 31, hi = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const int wr = wave >> 1, wc = wave & 1;
     const int t = xcd_remap(blockIdx.x, pp.nblocks);
     const int img = t / pp.tiles_per_img;
     const int ty = t - img * pp.tiles_per_img;
     const int Y0 = ty * TILE_H;
     const int up = ty > 0 ? t - 1 : -1, dn = ty + 1 < pp.tiles_per_img ? t + 1 : -1;
-
-    // ---- geometry that is identical for every layer (as ptrunk_kernel)
-    int goff[G::NJ];
-#pragma unroll
-    for (int j = 0; j < G::NJ; ++j) {
-        const int u0 = j * 256 + tid;
-        const int u = u0 < G::UNITS ? u0 : 0;
-        const int trow = u / (G::COLS * 4);
-        const int rem = u - trow * (G::COLS * 4);
-        const int pc = rem >> 2, ps = rem & 3;
-        goff[j] = trow * pp.row_b + pc * PIX_B + ((ps ^ ((pc >> 2) & 3)) << 4);
-    }
-    const bool tail_ok = (G::NJ - 1) * 256 + tid < G::UNITS;
-    int aoff[3][2];
-#pragma unroll
-    for (int dx = 0; dx < 3; ++dx) {
-        const int pc = wc * 32 + l31 + dx;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-            aoff[dx][ks] = wr * 4 * G::ROW_B + pc * PIX_B + (((ks * 2 + hi) ^ ((pc >> 2) & 3)) << 4);
-    }
-    const int woff = lane * 16;
     const long tile_off = (long)img * pp.img_b + (long)Y0 * pp.row_b;
 
     auto lds_addr = [](const char* p) { return (unsigned)(unsigned long long)(__attribute__((address_space(3))) const char*)p; };
@@ -173,8 +150,59 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
         const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)m), hi32 = __builtin_amdgcn_readfirstlane((unsigned)(m >> 32));
         return ((unsigned long long)hi32 << 32) | lo;
     };
-    const unsigned long long tail_mask = uni64(__builtin_amdgcn_ballot_w64(tail_ok));
     const unsigned long long w4_mask = uni64(wave < 2 ? ~0ull : 0ull);   // weight fragments 16, 17 of an 18-fragment chunk
+
+    // ---- the thread's geometry, identical for every layer (as ptrunk_kernel).  Set once here, and once more in front of the peeled last
+    // RDB (see there): variables of the kernel, set by one lambda
+    int tid, lane, l31, hi;
+    int goff[G::NJ];
+    int aoff[3][2];
+    int woff;
+    unsigned long long tail_mask;
+    int X;
+    // register-staged planes (S1, below): this lane's pixel record in a staged tile, row 0, and its two swizzled 16-byte slots
+    int soff, sswz[2];
+    // the zero border columns of the wave's 4 rows (a DMA-staged plane brings them along; a register-staged one must write them)
+    // (lanes 0..19: tile rows 0..4 for the upper pair of waves, 5..9 for the lower one, i.e. the own rows plus one halo row)
+    int boff;
+    // halo-only DMA: the 64 real pixels of tile row 0 / row 9 are exactly one 256-lane statement each (4 KiB, lane-linear in
+    // LDS behind the border pixel; the XOR swizzle is applied to the source address as everywhere)
+    int hoff[2];
+    auto thread_geometry = [&](const int tid_) {
+        tid = tid_;
+        lane = tid & 63;
+        l31 = lane & 31;
+        hi = lane >> 5;
+#pragma unroll
+        for (int j = 0; j < G::NJ; ++j) {
+            const int u0 = j * 256 + tid;
+            const int u = u0 < G::UNITS ? u0 : 0;
+            const int trow = u / (G::COLS * 4);
+            const int rem = u - trow * (G::COLS * 4);
+            const int pc = rem >> 2, ps = rem & 3;
+            goff[j] = trow * pp.row_b + pc * PIX_B + ((ps ^ ((pc >> 2) & 3)) << 4);
+        }
+        const bool tail_ok = (G::NJ - 1) * 256 + tid < G::UNITS;
+        tail_mask = uni64(__builtin_amdgcn_ballot_w64(tail_ok));
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) {
+            const int pc = wc * 32 + l31 + dx;
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks)
+                aoff[dx][ks] = wr * 4 * G::ROW_B + pc * PIX_B + (((ks * 2 + hi) ^ ((pc >> 2) & 3)) << 4);
+        }
+        woff = lane * 16;
+        X = wc * 32 + l31;
+        soff = (wr * 4 + 1) * G::ROW_B + (X + 1) * PIX_B;
+        sswz[0] = ((0 + hi) ^ (((X + 1) >> 2) & 3)) << 4;
+        sswz[1] = ((2 + hi) ^ (((X + 1) >> 2) & 3)) << 4;
+        boff = (wr * 5 + (lane >> 2)) * G::ROW_B + (wc ? (G::COLS - 1) * PIX_B : 0) + (lane & 3) * 16;
+        const int px = 1 + (tid >> 2), ps = tid & 3;
+#pragma unroll
+        for (int hrow = 0; hrow < 2; ++hrow)
+            hoff[hrow] = (hrow ? G::ROWS - 1 : 0) * pp.row_b + px * PIX_B + ((ps ^ ((px >> 2) & 3)) << 4);
+    };
+    thread_geometry(threadIdx.x);
 
     // ---- the LDS-DMA statement carries its own wait states: 5 between anything the compiler emitted in front of it and the
     // VMEM instruction (s_mov m0 + s_nop 3, or s_mov m0 + EXEC write + s_nop 2).  That covers "SALU writes M0 -> LDS-DMA" (1)
@@ -304,7 +332,6 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
     // ---- the RDB-level fp32 stream of this wave's 4 rows x 32 pixels x 64 channels: 128 registers per lane, conv5's
     // accumulator layout; loaded once from conv_first's pixel-order output
     floatx4 xres[2][4][4];
-    const int X = wc * 32 + l31;
     {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -325,20 +352,6 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
     // rows) still come by DMA.
     typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
     uintx4 x1p[4][2], X1r[4][2], X2r[4][2];   // [row][k-step]: x chunk 1 (written by conv5's epilogue), X1 / X2 (conv1's / conv2's epilogue)
-    const int soff = (wr * 4 + 1) * G::ROW_B + (X + 1) * PIX_B;                 // this lane's pixel record in a staged tile, row 0
-    const int sswz[2] = {((0 + hi) ^ (((X + 1) >> 2) & 3)) << 4, ((2 + hi) ^ (((X + 1) >> 2) & 3)) << 4};
-    // the zero border columns of the wave's 4 rows (a DMA-staged plane brings them along; a register-staged one must write them)
-    // (lanes 0..19: tile rows 0..4 for the upper pair of waves, 5..9 for the lower one, i.e. the own rows plus one halo row)
-    const int boff = (wr * 5 + (lane >> 2)) * G::ROW_B + (wc ? (G::COLS - 1) * PIX_B : 0) + (lane & 3) * 16;
-    // halo-only DMA: the 64 real pixels of tile row 0 / row 9 are exactly one 256-lane statement each (4 KiB, lane-linear in
-    // LDS behind the border pixel; the XOR swizzle is applied to the source address as everywhere)
-    int hoff[2];
-    {
-        const int px = 1 + (tid >> 2), ps = tid & 3;
-#pragma unroll
-        for (int hrow = 0; hrow < 2; ++hrow)
-            hoff[hrow] = (hrow ? G::ROWS - 1 : 0) * pp.row_b + px * PIX_B + ((ps ^ ((px >> 2) & 3)) << 4);
-    }
 #pragma unroll
     for (int i = 0; i < 4; ++i)      // x's second chunk as conv_first wrote it (fp16 plane 1 of dense[0])
 #pragma unroll
@@ -639,7 +652,8 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
     // one row of x (channel block mb) -> 16-bit fragments, kept (mb == 1), written into the next RDB's resident plane (mb == 0, to_lds) and
     // stored where somebody reads them from memory
     // (BF: bf16, except behind the last RDB -- f16out -- whose planes are the trunk's output: fp16 for conv_body)
-    auto x_row_out = [&](const int mb, const int i, char* obase, const bool st, const bool to_lds, const bool f16out) {
+    auto x_row_out = [&](const int mb, const int i, char* obase, const bool st, const bool to_lds, auto f16out_tag) {
+        constexpr bool f16out = decltype(f16out_tag)::value;
         const int Y = Y0 + wr * 4 + i;
         unsigned hp[4][2];
 #pragma unroll
@@ -686,8 +700,15 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
     // (x = 0.2 x + x_rrdb, the RRDB-level stream lives in memory): that is a SECOND pass over the registers behind a uniform
     // branch -- as a flag inside one body hipcc if-converted it into 128 selects, as two bodies the 160 live registers met in
     // phis and spilled.  In an RRDB-closing RDB the first pass stores nothing (its fp16 values are not final).
-    auto epi64 = [&](floatx16 (&acc)[2][4], char* obase, const bool r2, const bool r2_pixel, const bool x1_halo_only, const bool keep, const bool out_px,
-                     const bool f16out) {
+    // LAST (compile-time: the peeled last RDB): the new x goes out whole (conv_body reads it), as fp16 in the bf16 form, nothing is written
+    // into the resident plane, and a training forward's fp32 output goes to `xr` in pixel order; every other RDB stores only the rows a
+    // neighbour reads (training: whole planes, `keep`) and writes its own rows of the next resident plane.
+    auto epi64 = [&](auto last_tag, floatx16 (&acc)[2][4], char* obase, const bool r2, const bool r2_pixel) {
+        constexpr bool LAST = decltype(last_tag)::value;
+        constexpr bool x1_halo_only = P3_SKIPST && P3_S1 && !LAST;
+        using F16OUT = std::integral_constant<bool, BF && LAST>;
+        const bool keep = TRAIN && pp.keep_all != 0;
+        const bool out_px = LAST && TRAIN && pp.out_pixel != 0;
         floatx4 bias4[2][4];
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb)
@@ -731,7 +752,7 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
                     tt += bias4[mb][g];
                     xres[mb][i][g] = tt * 0.2f + xres[mb][i][g];
                 }
-                if (!r2) x_row_out(mb, i, obase, keep || (!P3_SEAM && mb == 0) || !x1_halo_only || halo, x1_halo_only, f16out);   // (RRDB-closing: the fp16 values are not final yet)
+                if (!r2) x_row_out(mb, i, obase, keep || (!P3_SEAM && mb == 0) || !x1_halo_only || halo, x1_halo_only, F16OUT{});   // (RRDB-closing: the fp16 values are not final yet)
             }
         }
         if (r2) {
@@ -742,7 +763,7 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
                 for (int mb = 0; mb < 2; ++mb) {
 #pragma unroll
                     for (int g = 0; g < 4; ++g) xres[mb][i][g] = xres[mb][i][g] * 0.2f + a2[slot][mb][g];
-                    x_row_out(mb, i, obase, keep || (!P3_SEAM && mb == 0) || !x1_halo_only || halo, x1_halo_only, f16out);
+                    x_row_out(mb, i, obase, keep || (!P3_SEAM && mb == 0) || !x1_halo_only || halo, x1_halo_only, F16OUT{});
                 }
                 // the RRDB-level stream goes back to memory (fragment order): private to this workgroup
                 // (out_px: behind the LAST RDB of a training forward it is the trunk's output: to `xr`, pixel order = NHWC)
@@ -774,7 +795,10 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
     stage_cold(dcur, smem, pp.layers[0].w, smem + stage_off(1, 0) + (P3_SEAM ? 0 : IN_EX), W5{});
     const int nrdb = pp.nlayers / 5;
     constexpr bool PAIR = P3_PAIR != 0;
-    for (int rdb = 0; rdb < nrdb; ++rdb) {
+    // ---- one RDB.  LAST (compile-time) = the last RDB of the launch: no successor, so no weight prefetch for one, no seam, no buffer
+    // hand-over, and conv5's epilogue in its last-RDB form (epi64)
+    auto rdb_body = [&](auto last_tag, const int rdb) {
+        constexpr bool LAST = decltype(last_tag)::value;
         const PLayer* T = pp.layers + rdb * 5;
         const int L0 = rdb * 5;
         int gs = 0;
@@ -861,7 +885,7 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
             if (P3_LAZYDRAIN) next_bias = bias_request(T[kk + 1].bias, kk == 3 ? 64 : 32);   // (older than the epilogue's stores)
             if (PROF) p2 = __builtin_amdgcn_s_memtime();
             uintx4 kept[4][2];
-            const bool halo_only = P3_SKIPST && P3_S1 && (kk == 0 || (P3_X2REG && kk == 1)) && !(P3_TRAIN && pp.keep_all);   // (training forward: whole planes)
+            const bool halo_only = P3_SKIPST && P3_S1 && (kk == 0 || (P3_X2REG && kk == 1)) && !(TRAIN && pp.keep_all);   // (training forward: whole planes)
             epi32(acc, dcur + (long)(2 + kk) * pp.plane_b - (long)Y0 * pp.row_b, kept, halo_only,
                   BW ? mcur + (long)(5 - kk) * pp.plane_b - (long)Y0 * pp.row_b : nullptr);
             if (kk == 0) {
@@ -1005,8 +1029,8 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
                 const char* st = smem + stage_off(2, 1);
                 if constexpr (P3_SEAM) {
                     // the next conv1's first weight chunk -> smem + IN_EX (dst = smem: run_step puts weights at dst + IN_EX); the last RDB has no
-                    // successor: it prefetches its own first chunk again (a select, not a branch: one step body), nobody reads it
-                    const char* nw5 = rdb + 1 < nrdb ? T[5].w : T[0].w;
+                    // successor: it prefetches its own first chunk again (the same step body, the same counted waits), nobody reads it
+                    const char* nw5 = LAST ? T[0].w : T[5].w;
                     run_step(C2{}, I0{}, W5{}, acc, st, st + IN_EX, nullptr, nw5, smem, x1p, F0{}, 0, Q1{}, Q0{}, IN_EX, smem);
                 } else {
                     run_step(C2{}, I0{}, W0{}, acc, st, st + IN_EX, nullptr, nullptr, smem, x1p, F0{}, 0, Q1{}, Q0{}, IN_EX, smem);
@@ -1014,14 +1038,13 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
             }
             const bool r2 = (rdb % 3) == 2;
             if (PROF) p2 = __builtin_amdgcn_s_memtime();
-            epi64(acc, dnxt - (long)Y0 * pp.row_b, r2, rdb == 2, P3_SKIPST && P3_S1 && rdb + 1 < nrdb, P3_TRAIN && pp.keep_all != 0,
-                  P3_TRAIN && pp.out_pixel != 0 && rdb + 1 == nrdb, BF && rdb + 1 == nrdb);   // (the last x goes out whole: conv_body reads it)
+            epi64(last_tag, acc, dnxt - (long)Y0 * pp.row_b, r2, rdb == 2);
             if (PROF) p3 = __builtin_amdgcn_s_memtime();
             // RDB seam: the next conv1's first chunk is THIS layer's output on the neighbours: publish now, then wait for them
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
             publish(L + 1);
-            if (rdb + 1 < nrdb) {
+            if constexpr (!LAST) {
                 poll_issue();
                 poll_check(std::integral_constant<int, 0>{}, L + 1);
                 if constexpr (P3_SEAM) {
@@ -1038,15 +1061,25 @@ __global__ __launch_bounds__(256, 1) void ptrunk3_kernel(const PParams pp) {
                 unsigned long long* q = pp.prof + ((long)blockIdx.x * pp.nlayers + L) * 6;
                 q[0] = p1; q[1] = p2; q[2] = p3; q[3] = (p1 - p0) | ((unsigned long long)(__builtin_amdgcn_s_memtime() - p3) << 32); q[4] = t_sync; q[5] = t_vm;
             }
-            if constexpr (BW) mcur += pp.mask_stride;
-            if (P3_TRAIN && pp.dense_stride) {      // (training forward: one dense buffer per RDB)
-                dcur = dnxt;
-                dnxt = dnxt + pp.dense_stride;
-            } else {
-                char* tmp = dcur;
-                dcur = dnxt;
-                dnxt = tmp;
+            if constexpr (!LAST) {
+                if constexpr (BW) mcur += pp.mask_stride;
+                if (TRAIN && pp.dense_stride) {      // (training forward: one dense buffer per RDB)
+                    dcur = dnxt;
+                    dnxt = dnxt + pp.dense_stride;
+                } else {
+                    char* tmp = dcur;
+                    dcur = dnxt;
+                    dnxt = tmp;
+                }
             }
         }
-    }
+    };
+    int rdb = 0;
+    for (; rdb + 1 < nrdb; ++rdb) rdb_body(std::false_type{}, rdb);
+    asm volatile("; ptrunk3: last RDB" ::: "memory");   // (a comment in the ISA text: where the loop form ends and the peeled form begins)
+    // The loop form reads the thread's geometry as addresses the compiler hoisted out of the loop; the straight-line peeled form would read
+    // the values they were MADE FROM, which then live through the whole loop beside them (4 VGPRs more than the 512 there are: scratch).
+    // Made again from the hardware lane number, nothing of the thread's geometry crosses the loop for the peeled form's sake.
+    thread_geometry(wave * 64 + (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
+    rdb_body(std::true_type{}, rdb);
 }
