@@ -1051,6 +1051,61 @@ int srbh_zone_hist(const void* v, int typeV, long row_strideV, const void* m, in
                    const int* edges, const int* edge_off, int Z, int E, const int* items, const int* item_off, int NI, int vthr, int mthr,
                    int bin_width, int nbins, long long* hist, void* ws, void* stream);
 
+/* ---- City validation: a predicted raster against a reference raster on the same grid, summed in exact integers (the reference's cal_rmse,
+ * demo_preprocess_height_v2.py:1389-1406, its per-cell compare_twotiff_valid* family and, at city scale, vtest_epoch2's HeightMetric per
+ * height class and SegmentationMetric of the class map; the exact rule below is this project's own; csrc/srbh_compare.hip) ------------------
+ * p: the predicted raster, r: the reference raster, m: an optional third raster (NULL: none; the class raster) -- logical shape (H, W),
+ * element type SRBH_GRID_U16 or SRBH_GRID_U8 each, read in place through its own ROW stride in ELEMENTS (>= W; the column stride is 1),
+ * aligned to the element size only.  All values are raster units; nothing is scaled.  d = p - r, signed.
+ * A pixel is COMPARED when it lies inside the raster (and inside the window, for srbh_pair_sums), the pair test of `mode` holds and
+ * (m == NULL or m > mthr).  With P := p > pthr and R := r > rthr the pair test is
+ *   SRBH_PAIR_ANY  P or R      SRBH_PAIR_BOTH  P and R      SRBH_PAIR_REF  R      SRBH_PAIR_PRED  P
+ * pthr, rthr and mthr lie in -1..65535; -1 makes a test always true, so ANY with (-1, -1) compares every pixel.
+ * Integers only: exact, independent of any order, bit-equal between runs; no floating point, no global atomics, no host synchronisation.
+ * The rasters are walked as srbh_window_sums walks v and m (16-byte groups of p's ADDRESS, the alignment taken per row; r and m follow with
+ * loads of element alignment; every load predicated on the rectangle AND the raster): no byte outside the rows of any of the three rasters
+ * is touched, whatever pos holds.
+ * Overflow: H * W < 2^31 and every value is below 2^16, so count and n stay below 2^31, the sums of p, r, |d| and |sum of d| below
+ * 65535 * 2^31 < 2^47, and the sums of p^2, r^2, p r and d^2 below 65535^2 * (2^31 - 1) < 2^32 * 2^31 = 2^63: every sum fits int64.  A
+ * group's sums of p, r, d and |d| (16 values below 2^16) are 32-bit, everything kept across groups is 64-bit; squares and products enter
+ * through 32 x 32 -> 64-bit multiply-adds.
+ *
+ * srbh_pair_sums: pos int32 [N][4] on the device, (xoff, yoff, xcount, ycount), clipped to the raster; out int64 [N][10] on the device,
+ * OVERWRITTEN:
+ *   out[n] = { count, n, sd, sad, sdd, sp, sr, spp, srr, spr }
+ * count = the window's pixels inside the raster (no test applies to it), n = the compared ones among them, and over the compared pixels
+ * sd = sum d, sad = sum |d|, sdd = sum d^2, sp = sum p, sr = sum r, spp = sum p^2, srr = sum r^2, spr = sum p r (all 0 when n == 0).
+ * One workgroup of 256 lanes per window, a shuffle tree per wave, the four waves through LDS; one launch, no atomics, no workspace.
+ *
+ * srbh_pair_class_sums: the whole raster (a sub-rectangle is a view).  edges: C int32 values ON THE HOST, strictly ascending,
+ * edges[0] == 0, 2 <= C <= 16.  The class of a value v is the number of k in 1 .. C - 1 with v >= edges[k]: values at or beyond the last
+ * edge fall in class C - 1.  For every compared pixel c = the class of r, pc = the value of m when m is given, else the class of p;
+ * { n, sd, sad, sdd } of class c are updated and cm[c][pc] is incremented.  A compared pixel with m >= C is counted in the four sums, in
+ * no column of cm, and in the counter bad.  out int64 [C * (4 + C) + 1] on the device, OVERWRITTEN: C rows
+ *   { n, sd, sad, sdd, cm[c][0], ..., cm[c][C - 1] }   then   bad
+ * (cm is [reference class][predicted class]).  With m as the class source mthr = -1 switches its masking off.  At most 2048 workgroups
+ * stride over the raster; each keeps the table in LDS (64-bit LDS integer atomics; a group of one value throughout is one update, and a
+ * lane carries the sums of its current class and the count of its current cm entry in registers and updates the table when they change) and
+ * stores it to its slot of ws; a second kernel adds
+ * the slots in slot order.  ws: srbh_pair_class_ws_bytes(H, W, C) bytes of device memory (0 for arguments the call would refuse), aligned
+ * to 8 bytes, no initialisation needed.
+ *
+ * Refused with SRBH_ERR_ARG, nothing launched: a null p, r, pos, out, edges or ws; int16, float32 or unknown type codes; H, W or N <= 0; a
+ * row stride below W; H * W >= 2^31; a raster not aligned to its element size; a threshold outside -1..65535; a mode outside 0..3; C
+ * outside 2..16; edges[0] != 0 or edges not strictly ascending; out or ws not aligned to 8 bytes.  The windows live on the device: the
+ * Python layer (city_compare.pair_sums) validates host windows and the size of a workspace. */
+#define SRBH_PAIR_ANY 0
+#define SRBH_PAIR_BOTH 1
+#define SRBH_PAIR_REF 2
+#define SRBH_PAIR_PRED 3
+int srbh_pair_sums(const void* p, int typeP, long row_strideP, const void* r, int typeR, long row_strideR, const void* m, int typeM,
+                   long row_strideM, int H, int W, const int* pos, int N, int mode, int pthr, int rthr, int mthr, long long* out,
+                   void* stream);
+size_t srbh_pair_class_ws_bytes(int H, int W, int C);
+int srbh_pair_class_sums(const void* p, int typeP, long row_strideP, const void* r, int typeR, long row_strideR, const void* m, int typeM,
+                         long row_strideM, int H, int W, const int* edges, int C, int mode, int pthr, int rthr, int mthr, long long* out,
+                         void* ws, void* stream);
+
 /* ---- The middle of an MBConv block in ONE launch per direction (round 4; efficientnet_pytorch MBConvBlock.forward between the expand and
  * the project conv, run by smp's encoder at mymodels.py:276): BatchNorm0 (training) + SiLU -> depthwise KxK, stride 1, "same" zero padding ->
  * BatchNorm1 (training) + SiLU (+ the plane means squeeze-and-excitation pools).  fp32 NCHW, square planes 2x2 / 4x4 / 8x8, K = 3 | 5.
