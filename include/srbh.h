@@ -1106,6 +1106,37 @@ int srbh_pair_class_sums(const void* p, int typeP, long row_strideP, const void*
                          long row_strideM, int H, int W, const int* edges, int C, int mode, int pthr, int rthr, int mthr, long long* out,
                          void* ws, void* stream);
 
+/* ---- Urban-centre validation: the pair sums above per POLYGON ZONE (the paper reports per urban centre; csrc/srbh_zone_compare.hip) -----
+ * p, r, m, their types and row strides, mode, pthr, rthr, mthr: as for srbh_pair_sums.  edges, edge_off, Z, E, items, item_off, NI: the
+ * device tables of srbh_zone_sums, unchanged (the same uploaded tables serve both).
+ * The rule is the conjunction of the two rules above, each unchanged: a pixel enters the sums when it is IN THE ZONE (int32 fixed point
+ * with 8 fractional bits, even-odd over all the zone's edges, the pixel's centre (x + 1/2, y + 1/2) decides, a centre on a left or top
+ * boundary is in, on a right or bottom boundary out) AND COMPARED (inside the raster, the pair test of `mode` holds, and m == NULL or
+ * m > mthr).  out int64 [Z][10] on the device, OVERWRITTEN:
+ *   out[z] = { count, n, sd, sad, sdd, sp, sr, spp, srr, spr }
+ * count = the zone's pixels inside the raster, as srbh_zone_sums defines it (no test of the comparison applies to it); n = the compared
+ * ones among them; over those sd = sum d (d = p - r, signed), sad = sum |d|, sdd = sum d^2, sp = sum p, sr = sum r, spp = sum p^2,
+ * srr = sum r^2, spr = sum p r (all 0 when n == 0).  A zone with no edge or no item gives zeros.
+ * Overflow: the argument of srbh_pair_sums.  H * W < 2^31 and a zone's items do not overlap, so a zone holds fewer than 2^31 pixels, and
+ * every value is below 2^16: count and n stay below 2^31, sp, sr, sad and |sd| below 65535 * 2^31 < 2^47, and spp, srr, spr and sdd below
+ * 65535^2 * (2^31 - 1) < 2^32 * 2^31 = 2^63: every sum fits int64, in an item's slot and in the zone's row alike.  A group's sums of p, r,
+ * d and |d| are 32-bit, everything kept across groups is 64-bit.
+ * One workgroup of 256 lanes per item: the LDS bitmap of srbh_zone_sums (toggles, suffix XOR), the walk of srbh_pair_sums with p as the
+ * raster that fixes the groups; a group's raster row is recovered once from its row pointer and addresses both the bitmap's row and m's;
+ * a group without a pixel in the zone loads nothing, and m is loaded only where a pixel of the zone passed the pair test.  Ten int64 per
+ * item go to its slot of ws (srbh_zone_pair_ws_bytes(NI) = NI * 10 * 8 bytes, 0 for NI <= 0; no initialisation needed), a second kernel
+ * adds each zone's slots in item order.  Integers only, no global atomics, no host synchronisation: exact, bit-equal between runs and
+ * independent of how the items are cut.  Wrong tables may give wrong sums; they never give a load outside the rasters' rows or the
+ * tables' own bytes, nor a store outside out / ws.
+ * Refused with SRBH_ERR_ARG, nothing launched, nothing written: a null p, r, table, out or ws; a type code that is not SRBH_GRID_U16 or
+ * SRBH_GRID_U8; m given with typeM 0, or typeM given without m; H or W <= 0; H * W >= 2^31; a row stride below W; a raster not aligned to
+ * its element size; edges not aligned to 16 bytes, another table not to 4, out or ws not to 8; Z, E or NI <= 0; a mode outside 0..3; a
+ * threshold outside -1..65535. */
+size_t srbh_zone_pair_ws_bytes(int NI);
+int srbh_zone_pair_sums(const void* p, int typeP, long row_strideP, const void* r, int typeR, long row_strideR, const void* m, int typeM,
+                        long row_strideM, int H, int W, const int* edges, const int* edge_off, int Z, int E, const int* items,
+                        const int* item_off, int NI, int mode, int pthr, int rthr, int mthr, long long* out, void* ws, void* stream);
+
 /* ---- The middle of an MBConv block in ONE launch per direction (round 4; efficientnet_pytorch MBConvBlock.forward between the expand and
  * the project conv, run by smp's encoder at mymodels.py:276): BatchNorm0 (training) + SiLU -> depthwise KxK, stride 1, "same" zero padding ->
  * BatchNorm1 (training) + SiLU (+ the plane means squeeze-and-excitation pools).  fp32 NCHW, square planes 2x2 / 4x4 / 8x8, K = 3 | 5.

@@ -20,8 +20,8 @@ the pair test of ``mode`` holds -- with ``P := p > pred_threshold`` and ``R := r
 kernels (csrc/srbh_compare.hip) work in integers only, so every sum is exact and bit-equal between runs.  Everything stays in RASTER
 UNITS: predict_city's height is ``round(10 h)``, the caller brings the reference to the same units, nothing here divides by ten.
 
-GPU only.  Polygon zones (a per-urban-centre RMSE on the zone kernel), rasters of another resolution and warping, int16 and float rasters,
-GeoTIFFs and shapefiles are out of scope."""
+GPU only.  The same sums per polygon zone (a per-urban-centre RMSE) are ``city_zone_compare``'s.  Rasters of another resolution and
+warping, int16 and float rasters, GeoTIFFs and shapefiles are out of scope."""
 import ctypes
 import math
 

@@ -20,7 +20,7 @@
 //   spp, srr, spr, sdd       <= 65535^2 * (2^31 - 1) < 2^32 * 2^31 = 2^63
 // so every sum fits int64.  Within a group (at most 16 pixels) the sums of p, r, d and |d| stay below 2^20 and are formed in 32 bits;
 // squares and products enter 64-bit lane sums through 32 x 32 -> 64-bit multiply-adds.
-#include "srbh_raster_walk.h"
+#include "srbh_pair_pieces.h"
 
 #ifndef SRBH_PAIR_CLASS_DIRECT
 #define SRBH_PAIR_CLASS_DIRECT 0      // developer A/B only: 1 = one LDS update per pixel and table entry, no combining in registers
@@ -33,61 +33,12 @@ constexpr int PC_MAX_C = 16;
 constexpr int PC_MAX_WGS = 2048;
 constexpr int PC_GROUPS_PER_LANE = 8;                  // a workgroup is worth launching for 256 * 8 groups of 16 bytes
 
-struct PairParams {
-    Rasters r;                      // a: the predicted raster p, b: the reference r
-    const unsigned char* m;         // NULL: no third raster
-    long rsM;                       // its row stride in elements
-    int mode, pthr, rthr, mthr;
-    int row_tz;                     // p's row stride in bytes = row_odd << row_tz,
-    unsigned long long row_inv;     // row_inv * row_odd == 1 modulo 2^64
-};
-
 struct ClassParams {
     int C;
     int edges[PC_MAX_C];            // edges[k] for k >= C: INT_MAX, which no value reaches
 };
 
 // ---- device ---------------------------------------------------------------------------------------------------------------------------------
-// bit j: pixel j of the group is compared.  wp, wr: the group's words of p and r; wm: of m, loaded only when a pixel passed the pair test
-template <int EP, int ER, int EM>
-__device__ __forceinline__ unsigned pair_select(const PairParams& q, const Group<EP, ER>& g, unsigned* wp, unsigned* wr, unsigned* wm) {
-    using G = Group<EP, ER>;
-    g.load_a(wp);
-    g.load_b(wr);
-    unsigned P = 0, R = 0;
-#pragma unroll
-    for (int j = 0; j < G::P; ++j) {
-        P |= ((int)group_pixel<EP>(wp, j) > q.pthr ? 1u : 0u) << j;
-        R |= ((int)group_pixel<ER>(wr, j) > q.rthr ? 1u : 0u) << j;
-    }
-    unsigned sel = q.mode == SRBH_PAIR_ANY ? (P | R) : q.mode == SRBH_PAIR_BOTH ? (P & R) : q.mode == SRBH_PAIR_REF ? R : P;
-    sel &= g.inside();
-    if (EM) {
-        constexpr int EMM = EM ? EM : 1;
-        if (!sel) return 0u;
-        const long y = (long)((((unsigned long long)(g.rowA - q.r.a)) >> q.row_tz) * q.row_inv);      // the group's raster row, in [0, H)
-        load_group<EMM, G::P, false>(q.m + y * q.rsM * EMM, g.c0, g.W, g.lo, g.hi, wm);
-        unsigned ms = 0;
-#pragma unroll
-        for (int j = 0; j < G::P; ++j) ms |= ((int)group_pixel<EMM>(wm, j) > q.mthr ? 1u : 0u) << j;
-        sel &= ms;
-    }
-    return sel;
-}
-
-struct PAcc {
-    int n;
-    long long sd;
-    unsigned long long sad, sdd, sp, sr, spp, srr, spr;
-    __device__ __forceinline__ PAcc down(int o) const {
-        return {__shfl_down(n, o, 64),   __shfl_down(sd, o, 64),  __shfl_down(sad, o, 64), __shfl_down(sdd, o, 64), __shfl_down(sp, o, 64),
-                __shfl_down(sr, o, 64),  __shfl_down(spp, o, 64), __shfl_down(srr, o, 64), __shfl_down(spr, o, 64)};
-    }
-    __device__ __forceinline__ void merge(const PAcc& o) {
-        n += o.n; sd += o.sd; sad += o.sad; sdd += o.sdd; sp += o.sp; sr += o.sr; spp += o.spp; srr += o.srr; spr += o.spr;
-    }
-};
-
 // EP, ER, EM: element sizes of p, r and m in bytes (EM == 0: no third raster)
 template <int EP, int ER, int EM>
 __global__ __launch_bounds__(256) void pair_sums_kernel(const PairParams q, const int* __restrict__ pos, long long* __restrict__ out) {
@@ -273,46 +224,6 @@ __global__ __launch_bounds__(256) void pair_class_fold_kernel(const unsigned lon
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------------
-inline bool pair_type_ok(int type) { return type == SRBH_GRID_U16 || type == SRBH_GRID_U8; }
-
-// the checks common to both entries; fills q.  SRBH_OK or SRBH_ERR_ARG (the error text is set)
-int pair_params(const char* who, const void* p, int typeP, long rsP, const void* r, int typeR, long rsR, const void* m, int typeM, long rsM,
-                int H, int W, int mode, int pthr, int rthr, int mthr, PairParams* q) {
-    SRBH_REQUIRE(p && r, "%s: null raster", who);
-    SRBH_REQUIRE(pair_type_ok(typeP) && pair_type_ok(typeR) && (!m || pair_type_ok(typeM)),
-                 "%s: element type typeP=%d typeR=%d typeM=%d; the rasters are uint16 (1) or uint8 (3) -- int16, float32 and unknown codes are "
-                 "refused", who, typeP, typeR, typeM);
-    SRBH_REQUIRE(mode >= SRBH_PAIR_ANY && mode <= SRBH_PAIR_PRED, "%s: mode=%d outside 0..3", who, mode);
-    SRBH_REQUIRE(pthr >= -1 && pthr <= 65535 && rthr >= -1 && rthr <= 65535 && mthr >= -1 && mthr <= 65535,
-                 "%s: a threshold (pthr=%d, rthr=%d, mthr=%d) outside -1..65535", who, pthr, rthr, mthr);
-    const int rc = rasters_checked(who, p, typeP, rsP, r, typeR, rsR, H, W, &q->r);
-    if (rc != SRBH_OK) return rc;
-    SRBH_REQUIRE(!m || rsM >= W, "%s: the third raster's row stride %ld is below W=%d", who, rsM, W);
-    SRBH_REQUIRE(!m || (uintptr_t)m % raster_esz(typeM) == 0, "%s: the third raster is not aligned to its element size", who);
-    q->m = (const unsigned char*)m;
-    q->rsM = m ? rsM : 0;
-    q->mode = mode; q->pthr = pthr; q->rthr = rthr; q->mthr = mthr;
-    unsigned long long s = (unsigned long long)rsP * (unsigned)raster_esz(typeP);      // > 0
-    q->row_tz = __builtin_ctzll(s);
-    s >>= q->row_tz;
-    unsigned long long inv = s;                                       // correct to 3 bits; each step doubles them
-    for (int i = 0; i < 5; ++i) inv *= 2ull - s * inv;
-    q->row_inv = inv;
-    return SRBH_OK;
-}
-
-// f(integral_constant EP, ER, EM) for the element sizes of the three rasters (EM == 0: no m)
-template <class F>
-inline void with_pair_sizes(int typeP, int typeR, const void* m, int typeM, F&& f) {
-    with_const<2>(raster_esz(typeP) - 1, [&](auto ep) {
-        return with_const<2>(raster_esz(typeR) - 1, [&](auto er) {
-            return with_const<3>(m ? raster_esz(typeM) : 0, [&](auto em) {
-                return f(std::integral_constant<int, decltype(ep)::value + 1>{}, std::integral_constant<int, decltype(er)::value + 1>{}, em), 0;
-            });
-        });
-    });
-}
-
 }  // namespace
 
 extern "C" int srbh_pair_sums(const void* p, int typeP, long row_strideP, const void* r, int typeR, long row_strideR, const void* m, int typeM,
