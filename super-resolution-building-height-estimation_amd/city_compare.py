@@ -29,8 +29,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .city_grid import _check_rasters, _check_windows, _on_device
-from .city_summary import _SUM_TYPES, block_sums
+from .city_grid import _check_rasters, _check_windows, _on_device, _workspace
+from .city_summary import _SUM_TYPES, _int_rows, block_sums
 
 __all__ = ["pair_sums", "errors_from_sums", "cell_errors", "class_sums", "city_validation", "block_errors", "MODES", "DEFAULT_EDGES"]
 
@@ -117,14 +117,9 @@ def class_sums(pred, ref, edges, build=None, mode="any", pred_threshold=-1, ref_
     H, W, mode, pthr, rthr, mthr = _rasters("class_sums", pred, ref, build, mode, pred_threshold, ref_threshold, mask_threshold)
     e = _edges("class_sums", edges)
     C = len(e)
-    if workspace is not None and not (torch.is_tensor(workspace) and workspace.is_cuda and workspace.is_contiguous()):
-        raise ValueError("class_sums: workspace must be a contiguous device buffer")
+    _workspace("class_sums", workspace)
     pred, rs_p, ref, rs_r, build, rs_m = _device_rasters("class_sums", pred, ref, build)
-    need = _lib.lib().srbh_pair_class_ws_bytes(H, W, C)
-    if workspace is None:
-        workspace = torch.empty(need // 8, dtype=torch.int64, device=pred.device)
-    elif not (workspace.device == pred.device and workspace.numel() * workspace.element_size() >= need and workspace.data_ptr() % 8 == 0):
-        raise ValueError(f"class_sums: workspace must be a contiguous device buffer of at least {need} bytes on {pred.device}, aligned to 8")
+    workspace = _workspace("class_sums", workspace, _lib.lib().srbh_pair_class_ws_bytes(H, W, C), pred.device)
     out = torch.empty(C * (4 + C) + 1, dtype=torch.int64, device=pred.device)
     with torch.cuda.device(pred.device):
         _lib.check(_lib.lib().srbh_pair_class_sums(*_abi(pred, rs_p, ref, rs_r, build, rs_m, H, W), (ctypes.c_int * C)(*e), C, mode, pthr,
@@ -157,11 +152,7 @@ def errors_from_sums(sums):
     ``rmse = sqrt(sdd / n)``, ``mean_pred``, ``mean_ref``, Pearson ``r = (n spr - sp sr) / sqrt((n spp - sp^2)(n srr - sr^2))`` and
     ``r2 = 1 - n sdd / (n srr - sr^2)`` (the coefficient of determination of pred as a predictor of ref).  NaN where n == 0 (count == 0
     for fraction) or the variance in a denominator is 0."""
-    sums = np.asarray(sums)
-    if sums.ndim != 2 or sums.shape[1] != 10 or not np.issubdtype(sums.dtype, np.integer):
-        raise ValueError(f"errors_from_sums: needs (N, 10) integers [count, n, sd, sad, sdd, sp, sr, spp, srr, spr] (got {sums.dtype} "
-                         f"{sums.shape})")
-    rows = [[int(v) for v in r] for r in sums.tolist()]
+    rows = _int_rows("errors_from_sums", sums, ("count", "n", "sd", "sad", "sdd", "sp", "sr", "spp", "srr", "spr"))
     out = {"n": np.array([r[1] for r in rows], dtype=np.int64), "count": np.array([r[0] for r in rows], dtype=np.int64)}
     vals = [_errors(*r) for r in rows]
     for k, name in enumerate(_FLOATS):

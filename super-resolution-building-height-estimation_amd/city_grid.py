@@ -114,6 +114,20 @@ def _on_device(fn, names, a, b):
     return out
 
 
+def _workspace(fn, workspace, need=0, device=None, align=8):
+    """the buffer an entry hands to libsrbh: ``workspace`` itself, judged, or a new one of ``need`` bytes where it is None.  Without
+    ``device`` -- an entry's early call, before it asks for a device -- only what needs none is judged: a contiguous device tensor"""
+    if workspace is None:
+        return None if device is None else torch.empty(max(need, 8), dtype=torch.uint8, device=device)
+    ok = torch.is_tensor(workspace) and workspace.is_cuda and workspace.is_contiguous()
+    if ok and device is not None:
+        ok = workspace.device == device and workspace.numel() * workspace.element_size() >= need and workspace.data_ptr() % align == 0
+    if not ok:
+        size = "" if device is None else f" of at least {need} bytes on {device}, aligned to {align}"
+        raise ValueError(f"{fn}: workspace must be a contiguous device buffer{size}")
+    return workspace
+
+
 def cell_counts(mask, pos, other=None, threshold=0, as_uint8=True):
     """-> device (N, 4) int64 ``[n_a, n_b, n_and, count]`` per window, one srbh_cell_counts launch on the current stream.
     ``mask`` / ``other``: (H, W) device tensors of uint8, uint16 or int16, read in place (stride 1 along W, any row stride: one band of

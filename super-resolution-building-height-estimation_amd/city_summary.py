@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .city_grid import _check_rasters, _check_windows, _on_device
+from .city_grid import _check_rasters, _check_windows, _on_device, _workspace
 
 __all__ = ["window_sums", "block_sums", "value_histogram", "heights_from_sums", "cell_heights", "aggregate_city", "city_summary"]
 
@@ -46,6 +46,14 @@ def _rasters(fn, value, mask, value_threshold, mask_threshold):
     if not (-1 <= vthr <= 65535 and -1 <= mthr <= 65535):
         raise ValueError(f"{fn}: a threshold ({vthr}, {mthr}) outside -1..65535")
     return H, W, vthr, mthr
+
+
+def _bins(fn, bin_width, nbins):
+    """a histogram's division judged -> (bin_width, nbins) as ints"""
+    for name, v, hi in (("bin_width", bin_width, 65535), ("nbins", nbins, MAX_BINS)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= hi:
+            raise ValueError(f"{fn}: {name}={v!r} outside 1..{hi}")
+    return int(bin_width), int(nbins)
 
 
 def _abi(value, rs_v, mask, rs_m, H, W):
@@ -98,17 +106,9 @@ def value_histogram(value, bin_width=1, nbins=256, mask=None, value_threshold=0,
     ``value_histogram(build, 1, 7, value_threshold=-1)`` gives the class counts.  ``workspace``: optional device buffer of at least
     srbh_value_hist_ws_bytes bytes to reuse between calls (its content does not matter)."""
     H, W, vthr, mthr = _rasters("value_histogram", value, mask, value_threshold, mask_threshold)
-    for name, v, hi in (("bin_width", bin_width, 65535), ("nbins", nbins, MAX_BINS)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= hi:
-            raise ValueError(f"value_histogram: {name}={v!r} outside 1..{hi}")
-    bin_width, nbins = int(bin_width), int(nbins)
+    bin_width, nbins = _bins("value_histogram", bin_width, nbins)
     value, rs_v, mask, rs_m = _on_device("value_histogram", _NAMES, value, mask)
-    need = _lib.lib().srbh_value_hist_ws_bytes(H, W, nbins)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=value.device)
-    elif not (torch.is_tensor(workspace) and workspace.is_cuda and workspace.device == value.device and workspace.is_contiguous()
-              and workspace.numel() * workspace.element_size() >= need and workspace.data_ptr() % 4 == 0):
-        raise ValueError(f"value_histogram: workspace must be a contiguous device buffer of at least {need} bytes on {value.device}")
+    workspace = _workspace("value_histogram", workspace, _lib.lib().srbh_value_hist_ws_bytes(H, W, nbins), value.device, align=4)
     hist = torch.empty(nbins, dtype=torch.int64, device=value.device)
     with torch.cuda.device(value.device):
         _lib.check(_lib.lib().srbh_value_hist(*_abi(value, rs_v, mask, rs_m, H, W), vthr, mthr, bin_width, nbins, hist.data_ptr(),
@@ -125,14 +125,19 @@ def _mean_std(n, s, q):
     return s / n, math.sqrt((n * q - s * s) / (n * n))
 
 
+def _int_rows(fn, sums, columns):
+    """an (N, K) integer table on the host, K = len(columns) -> its rows as lists of Python integers, or ValueError"""
+    sums = np.asarray(sums)
+    if sums.ndim != 2 or sums.shape[1] != len(columns) or not np.issubdtype(sums.dtype, np.integer):
+        raise ValueError(f"{fn}: needs (N, {len(columns)}) integers [{', '.join(columns)}] (got {sums.dtype} {sums.shape})")
+    return [[int(v) for v in r] for r in sums.tolist()]
+
+
 def heights_from_sums(sums):
     """(N, 5) integers ``[count, n, sum, sumsq, max]`` (window_sums' rows, on the host) -> dict of numpy arrays, one entry per window:
     ``n``, ``count``, ``max`` int64; ``fraction = n / count``, ``mean = sum / n`` and ``std``, the population standard deviation
     sqrt((n sumsq - sum^2) / n^2), float64 in raster units.  n == 0 gives NaN for mean and std, count == 0 for fraction."""
-    sums = np.asarray(sums)
-    if sums.ndim != 2 or sums.shape[1] != 5 or not np.issubdtype(sums.dtype, np.integer):
-        raise ValueError(f"heights_from_sums: needs (N, 5) integers [count, n, sum, sumsq, max] (got {sums.dtype} {sums.shape})")
-    rows = [[int(v) for v in r] for r in sums.tolist()]
+    rows = _int_rows("heights_from_sums", sums, ("count", "n", "sum", "sumsq", "max"))
     out = {"n": np.array([r[1] for r in rows], dtype=np.int64), "count": np.array([r[0] for r in rows], dtype=np.int64),
            "max": np.array([r[4] for r in rows], dtype=np.int64)}
     out["fraction"] = np.array([r[1] / r[0] if r[0] else math.nan for r in rows], dtype=np.float64)

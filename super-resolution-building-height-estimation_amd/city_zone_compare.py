@@ -19,13 +19,12 @@ it.  ``d = pred - ref``, signed.  Raster units throughout.
 
 GPU only.  A per-zone ``class_sums`` (a HeightMetric per centre), a reference raster of another resolution and warping, int16 and float
 rasters, shapefiles and GeoTIFFs are out of scope."""
-import numpy as np
 import torch
 
 from . import _lib
 from .city_compare import _abi, _device_rasters, _rasters, errors_from_sums
-from .city_zones import ITEM_PIXELS, Zones, _tables, _workspace, zone_histogram, zone_sums
-from .city_summary import heights_from_sums
+from .city_grid import _workspace
+from .city_zones import ITEM_PIXELS, _centre_table, _check_zones, _tables
 
 __all__ = ["zone_pair_sums", "zone_errors", "urban_centre_validation"]
 
@@ -42,18 +41,12 @@ def zone_pair_sums(pred, ref, zones, mask=None, mode="any", pred_threshold=0, re
     reuse between calls (srbh_zone_pair_ws_bytes(number of items) bytes; its content does not matter)."""
     fn = "zone_pair_sums"
     H, W, mode, pthr, rthr, mthr = _rasters(fn, pred, ref, mask, mode, pred_threshold, ref_threshold, mask_threshold)
-    if isinstance(item_pixels, bool) or not isinstance(item_pixels, (int, np.integer)) or item_pixels < 1:
-        raise ValueError(f"{fn}: item_pixels={item_pixels!r} must be an integer >= 1")
-    if not isinstance(zones, Zones):
-        raise TypeError(f"{fn}: zones must come from zone_edges")
-    if len(zones) < 1:
-        raise ValueError(f"{fn}: no zones")
-    if workspace is not None and not (torch.is_tensor(workspace) and workspace.is_cuda and workspace.is_contiguous()):
-        raise ValueError(f"{fn}: workspace must be a contiguous device buffer")
+    item_pixels = _check_zones(fn, zones, item_pixels)
+    _workspace(fn, workspace)                                            # (before a device is asked for)
     pred, rs_p, ref, rs_r, mask, rs_m = _device_rasters(fn, pred, ref, mask)
     device = pred.device
     with torch.cuda.device(device):
-        ptrs, Z, E, NI = _tables(zones, H, W, int(item_pixels), device)
+        ptrs, Z, E, NI = _tables(zones, H, W, item_pixels, device)
     out = torch.empty((Z, 10), dtype=torch.int64, device=device)
     if E == 0 or NI == 0:                                                 # nothing of any zone lies inside the raster
         return out.zero_()
@@ -78,15 +71,8 @@ def urban_centre_validation(height, ref, build, zones, bin_width=10, nbins=256, 
     ``rmse``, ``mean_pred``, ``mean_ref``, ``r``, ``r2`` and ``n_compared`` -- zone_errors' numbers under cell_errors' defaults (the
     pixels where either height is > 0 and, with ``build``, class > 0).  Four calls (three without ``build``) on one set of uploaded
     tables, ONE torch.cat and ONE device-to-host copy for everything."""
-    parts = [zone_sums(height, zones, build), zone_histogram(height, zones, bin_width, nbins, build)]
-    if build is not None:
-        parts.append(zone_histogram(build, zones, 1, num_class, value_threshold=-1))
-    parts.append(zone_pair_sums(height, ref, zones, build))
-    flat = torch.cat(parts, dim=1).cpu().numpy()
-    out = heights_from_sums(flat[:, :5])
-    out["hist"] = flat[:, 5:5 + nbins].copy()
-    out["class_counts"] = None if build is None else flat[:, 5 + nbins:-10].copy()
-    err = errors_from_sums(flat[:, -10:])
+    out, sums = _centre_table(height, build, zones, bin_width, nbins, num_class, lambda: zone_pair_sums(height, ref, zones, build))
+    err = errors_from_sums(sums)
     for name in _ERROR_NAMES:
         out[name] = err[name]
     out["n_compared"] = err["n"]

@@ -26,8 +26,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .city_grid import _on_device
-from .city_summary import MAX_BINS, _NAMES, _abi, _rasters, heights_from_sums
+from .city_grid import _on_device, _workspace
+from .city_summary import _NAMES, _abi, _bins, _rasters, heights_from_sums
 
 __all__ = ["Zones", "zone_edges", "zone_items", "zone_sums", "zone_histogram", "zone_heights", "zonal_fields", "urban_centre_table"]
 
@@ -142,28 +142,25 @@ def _tables(zones, H, W, item_pixels, device):
     return hit[1:]
 
 
-def _workspace(fn, workspace, need, device):
-    if workspace is None:
-        return torch.empty(max(need, 8), dtype=torch.uint8, device=device)
-    if not (torch.is_tensor(workspace) and workspace.is_cuda and workspace.device == device and workspace.is_contiguous()
-            and workspace.numel() * workspace.element_size() >= need and workspace.data_ptr() % 8 == 0):
-        raise ValueError(f"{fn}: workspace must be a contiguous device buffer of at least {need} bytes on {device}")
-    return workspace
-
-
-def _prepare(fn, value, zones, mask, value_threshold, mask_threshold, item_pixels):
-    """the argument path of both entries: everything that needs no device first -> (the eight leading ABI arguments, the table
-    arguments, vthr, mthr, the device)"""
-    H, W, vthr, mthr = _rasters(fn, value, mask, value_threshold, mask_threshold)
+def _check_zones(fn, zones, item_pixels):
+    """the zone arguments of an entry (here and in city_zone_compare), judged without a device -> item_pixels as int"""
     if isinstance(item_pixels, bool) or not isinstance(item_pixels, (int, np.integer)) or item_pixels < 1:
         raise ValueError(f"{fn}: item_pixels={item_pixels!r} must be an integer >= 1")
     if not isinstance(zones, Zones):
         raise TypeError(f"{fn}: zones must come from zone_edges")
     if len(zones) < 1:
         raise ValueError(f"{fn}: no zones")
+    return int(item_pixels)
+
+
+def _prepare(fn, value, zones, mask, value_threshold, mask_threshold, item_pixels):
+    """the argument path of both entries: everything that needs no device first -> (the eight leading ABI arguments, the table
+    arguments, vthr, mthr, the device)"""
+    H, W, vthr, mthr = _rasters(fn, value, mask, value_threshold, mask_threshold)
+    item_pixels = _check_zones(fn, zones, item_pixels)
     value, rs_v, mask, rs_m = _on_device(fn, _NAMES, value, mask)
     with torch.cuda.device(value.device):
-        ptrs, Z, E, NI = _tables(zones, H, W, int(item_pixels), value.device)
+        ptrs, Z, E, NI = _tables(zones, H, W, item_pixels, value.device)
     return _abi(value, rs_v, mask, rs_m, H, W), (ptrs[0], ptrs[1], Z, E, ptrs[2], ptrs[3], NI), vthr, mthr, value.device
 
 
@@ -190,10 +187,7 @@ def zone_histogram(value, zones, bin_width=1, nbins=256, mask=None, value_thresh
     ``zone_histogram(height, zones, 10, 256, build)`` is each urban centre's height histogram in the 256-bin layout of bh_stats_*.txt,
     ``zone_histogram(build, zones, 1, 7, value_threshold=-1)`` its class counts."""
     fn = "zone_histogram"
-    for name, v, hi in (("bin_width", bin_width, 65535), ("nbins", nbins, MAX_BINS)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= hi:
-            raise ValueError(f"{fn}: {name}={v!r} outside 1..{hi}")
-    bin_width, nbins = int(bin_width), int(nbins)
+    bin_width, nbins = _bins(fn, bin_width, nbins)
     abi, tab, vthr, mthr, device = _prepare(fn, value, zones, mask, value_threshold, mask_threshold, item_pixels)
     Z, E, NI = tab[2], tab[3], tab[6]
     hist = torch.empty((Z, nbins), dtype=torch.int64, device=device)
@@ -221,16 +215,25 @@ def zonal_fields(value, zones):
     return {"sum": s[:, 1].copy(), "count": s[:, 0].copy()}
 
 
+def _centre_table(height, build, zones, bin_width, nbins, num_class, more=None):
+    """urban_centre_table's calls, then ``more()``'s device (Z, k) table where one is asked for; ONE torch.cat and ONE device-to-host
+    copy for everything -> (urban_centre_table's dict, the k columns of ``more`` as a numpy array)"""
+    parts = [zone_sums(height, zones, build), zone_histogram(height, zones, bin_width, nbins, build)]
+    if build is not None:
+        parts.append(zone_histogram(build, zones, 1, num_class, value_threshold=-1))
+    if more is not None:
+        parts.append(more())
+    flat = torch.cat(parts, dim=1).cpu().numpy()
+    end = flat.shape[1] - (0 if more is None else parts[-1].shape[1])
+    out = heights_from_sums(flat[:, :5])
+    out["hist"] = flat[:, 5:5 + nbins].copy()
+    out["class_counts"] = None if build is None else flat[:, 5 + nbins:end].copy()
+    return out, flat[:, end:]
+
+
 def urban_centre_table(height, build, zones, bin_width=10, nbins=256, num_class=7):
     """The urbanarea_meanstd row of each zone: dict of numpy arrays with one entry per zone -- ``mean``, ``std``, ``max``, ``n``,
     ``count``, ``fraction`` as zone_heights gives them, ``hist`` (Z, nbins) int64 (the zone's height histogram,
     zone_histogram(height, zones, bin_width, nbins, build)) and ``class_counts`` (Z, num_class) int64 (every pixel of the zone by class,
     the last class open; None without ``build``).  Three calls, one read-back."""
-    parts = [zone_sums(height, zones, build), zone_histogram(height, zones, bin_width, nbins, build)]
-    if build is not None:
-        parts.append(zone_histogram(build, zones, 1, num_class, value_threshold=-1))
-    flat = torch.cat(parts, dim=1).cpu().numpy()
-    out = heights_from_sums(flat[:, :5])
-    out["hist"] = flat[:, 5:5 + nbins].copy()
-    out["class_counts"] = None if build is None else flat[:, 5 + nbins:].copy()
-    return out
+    return _centre_table(height, build, zones, bin_width, nbins, num_class)[0]

@@ -11,7 +11,7 @@
 //
 // The walk is srbh_raster_walk.h's (p is its raster a, r its raster b; why no load leaves a raster is argued there).  The third raster is
 // not part of Rasters / Group: a group's row index is recovered from its row pointer (an exact division by p's row stride in bytes: a
-// shift and a multiplication by the odd part's inverse modulo 2^64, as srbh_zones.hip does), and m's pixels of the same columns are
+// shift and a multiplication by the odd part's inverse modulo 2^64, srbh_raster_walk.h's RowDiv), and m's pixels of the same columns are
 // fetched by load_group under the same predicates -- m's rows are addressed through its own stride, which the host checks to be >= W.
 //
 // Overflow.  H * W < 2^31 (the host requires it) and every value is below 2^16:
@@ -44,7 +44,7 @@ template <int EP, int ER, int EM>
 __global__ __launch_bounds__(256) void pair_sums_kernel(const PairParams q, const int* __restrict__ pos, long long* __restrict__ out) {
     using G = Group<EP, ER>;
     const Rect w = clip_window(pos + 4 * (long)blockIdx.x, q.r.H, q.r.W);
-    PAcc a = {0, 0ll, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+    PAcc a = {};
     if (w.any) {                                                      // uniform
         walk_rect<EP, ER>(q.r, w.x0, w.x1, w.y0, w.rows, threadIdx.x, 256, [&](const G& g) {
             unsigned wp[G::WORDS_A], wr[G::WORDS_B], wm[G::P * (EM ? EM : 1) / 4];
@@ -75,19 +75,7 @@ __global__ __launch_bounds__(256) void pair_sums_kernel(const PairParams q, cons
         });
     }
     fold_team<256>(a);
-    if (threadIdx.x == 0) {
-        long long* o = out + 10 * (long)blockIdx.x;
-        o[0] = (long long)(w.x1 - w.x0) * w.rows;
-        o[1] = a.n;
-        o[2] = a.sd;
-        o[3] = (long long)a.sad;
-        o[4] = (long long)a.sdd;
-        o[5] = (long long)a.sp;
-        o[6] = (long long)a.sr;
-        o[7] = (long long)a.spp;
-        o[8] = (long long)a.srr;
-        o[9] = (long long)a.spr;
-    }
+    if (threadIdx.x == 0) a.store(out + 10 * (long)blockIdx.x, (long long)(w.x1 - w.x0) * w.rows);
 }
 
 // ---- per class ------------------------------------------------------------------------------------------------------------------------------

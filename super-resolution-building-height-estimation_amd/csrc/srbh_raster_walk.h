@@ -1,6 +1,7 @@
-// srbh_raster_walk.h -- how the city kernels (srbh_cells.hip, srbh_summary.hip) read a rectangle of one or two (H, W) integer rasters in
-// place: the group loader, the walk of a rectangle by a team of lanes, the clip of a window to the raster, the fold of a team's partials,
-// and the host checks and element-size dispatch of their entry points.
+// srbh_raster_walk.h -- how the city kernels (srbh_cells.hip, srbh_summary.hip, and the zone and pair kernels through their own headers)
+// read a rectangle of one or two (H, W) integer rasters in place: the group loader, the walk of a rectangle by a team of lanes, the clip
+// of a window to the raster, the fold of a team's partials, the row divisor that gives a group's row back from its row pointer, and the
+// host checks and element-size dispatch of their entry points.
 //
 // The walk and why no load leaves a raster.  A rectangle [x0, x1) x [y0, y0 + rows) INSIDE the raster is cut, row by row, into groups of
 // P = 16 / sizeof(element of a) pixels that start on 16-byte boundaries of a's ADDRESS: xoff = k * 56, an odd W and a cropped view give
@@ -28,8 +29,23 @@ struct Rasters {
     int H, W;
 };
 
+// The exact division of a byte offset inside raster a by its row stride, for the kernels that recover a group's row from its row pointer:
+// the stride in bytes is odd << tz, and inv * odd == 1 modulo 2^64.
+struct RowDiv {
+    int tz;
+    unsigned long long inv;
+};
+
 // ---- host: what the entry points of both files check and choose alike -------------------------------------------------------------------
 inline int raster_esz(int type) { return type == SRBH_GRID_U8 ? 1 : 2; }
+
+inline RowDiv row_div(unsigned long long stride_bytes) {              // > 0
+    const int tz = __builtin_ctzll(stride_bytes);
+    const unsigned long long odd = stride_bytes >> tz;
+    unsigned long long inv = odd;                                     // correct to 3 bits; each step doubles them
+    for (int i = 0; i < 5; ++i) inv *= 2ull - odd * inv;
+    return {tz, inv};
+}
 
 // The checks common to every entry, made after the entry has judged the type codes (the accepted sets differ); fills r.  SRBH_OK or
 // SRBH_ERR_ARG (the error text is set, `who` in front).  b == NULL makes typeB and rsB irrelevant.
@@ -91,6 +107,9 @@ __device__ __forceinline__ void load_group(const unsigned char* row, int c0, int
         }
     }
 }
+
+// the row whose first byte lies `bytes` behind the raster's: bytes is a whole multiple of the stride d was made from
+__device__ __forceinline__ long row_index(const RowDiv& d, unsigned long long bytes) { return (long)((bytes >> d.tz) * d.inv); }
 
 // One (row, group) of a walk, handed to its functor: nothing is loaded until the functor asks, so it decides when b's group is in
 // registers (a client that thresholds a's group first keeps one group live, not two).

@@ -1,11 +1,13 @@
 // srbh_zone_bitmap.h -- what the polygon-zone kernels (srbh_zones.hip, srbh_zone_compare.hip) share: the device tables of the zones, the
-// LDS bitmap of a batch of rows (the edges' toggles, then the suffix XOR that turns them into the in-zone mask), the checked range of a
-// zone's items, and the host check of the tables.  The rule is stated in srbh_zones.hip and, in full, in include/srbh.h.
+// LDS bitmap of a batch of rows (the edges' toggles, then the suffix XOR that turns them into the in-zone mask), the walk of one item
+// that hands a client the groups with a pixel in the zone (zone_item_walk: the memory-safety argument of both files is stated there), the
+// checked range of a zone's items, the kernel that adds each zone's items, and the host check of the tables.  The rule is stated in
+// srbh_zones.hip and, in full, in include/srbh.h.
 //
 // Everything sits in the including file's own anonymous namespace, as it did in srbh_zones.hip: ZoneTables is a kernel parameter, and its
 // name is part of the kernels' symbols.
 #pragma once
-#include "srbh_summary_select.h"
+#include "srbh_raster_walk.h"
 
 namespace {
 using namespace srbh;
@@ -20,8 +22,7 @@ struct ZoneTables {
     const int* items;               // [NI][5] (zone, xoff, yoff, xcount, ycount)
     const int* item_off;            // [Z + 1]
     int Z, E, NI;
-    int row_tz;                     // the value raster's row stride in bytes = row_odd << row_tz,
-    unsigned long long row_inv;     // row_inv * row_odd == 1 modulo 2^64
+    RowDiv row;                     // of the row stride in bytes of the walk's raster a
 };
 
 #if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
@@ -96,24 +97,94 @@ __device__ __forceinline__ void zone_items(const ZoneTables& z, int zone, int* i
     *i0 = ok ? a : 0;
     *i1 = ok ? b : 0;
 }
+
+// One item, by its workgroup of 256 lanes (every lane calls): f(g, y, zb) once per (row, group) of this lane that has a pixel in the zone
+// -- g the group of walk_rect<EA, EB> over r, y its raster row, bit j of zb: pixel j of the group lies in the zone and inside the raster.
+// bm: BM_WORDS + 1 words of LDS (+ 1: a group's bits are read as a pair of words).  The item's band is done in batches of rows x segments
+// of columns that fit the bitmap: zeroed, toggled by the zone's edges, turned into the in-zone mask by the suffix XOR, then walked.
+//
+// Memory safety.  The item is read at `item` < NI (the caller's blockIdx) and clip_window cuts it to the raster in 64 bits whatever it
+// holds; the zone's edge range is used only where 0 <= zone < Z and 0 <= a <= b <= E, so no content of the tables leads outside them.
+// walk_rect's groups lie in the rows [yb, yb + rb) of the batch, and the row y that a group's row pointer gives (an exact division, z.row
+// being made from r's stride of a) is that row: the bitmap row y - yb lies in [0, rb), rb wpr <= BM_WORDS.  A group's first column lies
+// in (xs - P, xs + segw), so the word pair read ends at word (rb - 1) wpr + (segw - 1) / 32 + 1 <= BM_WORDS at most: inside bm, whose
+// last word is kept 0.  A group with no pixel in the zone loads nothing of the rasters.
+template <int EA, int EB, class F>
+__device__ __forceinline__ void zone_item_walk(const Rasters& r, const ZoneTables& z, long item, unsigned* bm, F&& f) {
+    using G = Group<EA, EB>;
+    const int t = threadIdx.x;
+    if (t == 0) bm[BM_WORDS] = 0u;
+    const int* q = z.items + 5 * item;
+    const int zone = q[0];
+    const Rect w = clip_window(q + 1, r.H, r.W);
+    int e0 = 0, e1 = 0;
+    if (zone >= 0 && zone < z.Z) {
+        const int a = z.edge_off[zone], b = z.edge_off[zone + 1];
+        if (a >= 0 && a <= b && b <= z.E) { e0 = a; e1 = b; }
+    }
+    if (!(w.any && e1 > e0)) return;                                  // uniform
+    const int width = w.x1 - w.x0;
+    const int full = (int)(((long)width + 31) >> 5);
+    const int wpr = full < BM_MAX_WPR ? full : BM_MAX_WPR, segw = wpr * 32, rbmax = BM_WORDS / wpr;
+    for (long done = 0; done < w.rows; done += rbmax) {
+        const int yb = w.y0 + (int)done, left = w.rows - (int)done, rb = left < rbmax ? left : rbmax;
+        for (long xl = w.x0; xl < w.x1; xl += segw) {
+            const int xs = (int)xl, xe = xl + segw < w.x1 ? (int)(xl + segw) : w.x1;
+            __syncthreads();                                          // the walk before is done with bm
+            for (int i = t; i < rb * wpr; i += 256) bm[i] = 0u;
+            __syncthreads();
+            toggle_edges(z.edges, e0, e1, yb, rb, xs, xe, wpr, bm);
+            __syncthreads();
+            suffix_xor_rows(bm, rb, wpr);
+            __syncthreads();
+            walk_rect<EA, EB>(r, xs, xe, yb, rb, t, 256, [&](const G& g) {
+                const long y = row_index(z.row, (unsigned long long)(g.rowA - r.a));      // the raster row, in [yb, yb + rb)
+                const unsigned* brow = bm + ((int)y - yb) * wpr;
+                const int off = g.c0 - xs;                            // in (-P, segw)
+                unsigned zb;
+                if (off >= 0) {
+                    const unsigned long long pair = brow[off >> 5] | ((unsigned long long)brow[(off >> 5) + 1] << 32);
+                    zb = (unsigned)(pair >> (off & 31));
+                } else {
+                    zb = brow[0] << -off;
+                }
+                zb &= g.inside();                                     // (bits beyond xe belong to the next row or are the suffix's spill)
+                if (!zb) return;
+                f(g, y, zb);
+            });
+        }
+    }
+}
+
+// A lane per zone: its items' rows of K words in ws added in item order to row `zone` of out; column MAXCOL (-1: none) takes the largest
+template <int K, int MAXCOL>
+__global__ __launch_bounds__(256) void zone_fold_kernel(const ZoneTables z, const long long* __restrict__ ws, long long* __restrict__ out) {
+    const long zone = blockIdx.x * 256L + threadIdx.x;
+    if (zone >= z.Z) return;
+    int i0, i1;
+    zone_items(z, (int)zone, &i0, &i1);
+    long long s[K] = {};
+    for (int i = i0; i < i1; ++i) {
+        const long long* a = ws + K * (long)i;
+#pragma unroll
+        for (int k = 0; k < K; ++k) s[k] = k == MAXCOL ? (s[k] > a[k] ? s[k] : a[k]) : s[k] + a[k];
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) out[K * zone + k] = s[k];
+}
 #endif
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------------
-// the checks of the tables; fills z.  Of p only the value raster's row stride is read (p.r.rsA elements of typeV)
+// the checks of the tables; fills z.  stride_bytes: the row stride of the raster that the item kernel walks as raster a (> 0)
 int zone_tables(const char* who, const int* edges, const int* edge_off, int Z, int E, const int* items, const int* item_off, int NI,
-                const SumParams& p, int typeV, ZoneTables* z) {
+                unsigned long long stride_bytes, ZoneTables* z) {
     SRBH_REQUIRE(edges && edge_off && items && item_off, "%s: null table", who);
     SRBH_REQUIRE(Z > 0 && E > 0 && NI > 0, "%s: Z=%d, E=%d and the item count %d must be positive", who, Z, E, NI);
     SRBH_REQUIRE((uintptr_t)edges % 16 == 0 && (uintptr_t)edge_off % 4 == 0 && (uintptr_t)items % 4 == 0 && (uintptr_t)item_off % 4 == 0,
                  "%s: edges must be aligned to 16 bytes, the other tables to 4", who);
     z->edges = (const int4*)edges; z->edge_off = edge_off; z->items = items; z->item_off = item_off;
     z->Z = Z; z->E = E; z->NI = NI;
-    unsigned long long s = (unsigned long long)p.r.rsA * (unsigned)raster_esz(typeV);      // > 0
-    z->row_tz = __builtin_ctzll(s);
-    s >>= z->row_tz;
-    unsigned long long inv = s;                                       // correct to 3 bits; each step doubles them
-    for (int i = 0; i < 5; ++i) inv *= 2ull - s * inv;
-    z->row_inv = inv;
+    z->row = row_div(stride_bytes);
     return SRBH_OK;
 }
 

@@ -20,9 +20,11 @@
 //   3. walk_rect walks the batch; a group's row is recovered from its row pointer (an exact division by the row stride: a multiplication
 //      by the stride's inverse modulo 2^64), the zone's bits of its P columns are ANDed into the selection.  A group with no pixel in the
 //      zone loads nothing.
-// Loads of the rasters are walk_rect's: the memory-safety argument of srbh_raster_walk.h carries over untouched.  The tables are read
-// through checked indices only, so no content of theirs leads outside them, the rasters' rows, ws or out.  No global atomics, no host
+// The three steps are zone_item_walk's (srbh_zone_bitmap.h), which srbh_zone_compare.hip walks too; the kernel here keeps what it does
+// with a group that has a pixel in the zone.  Loads of the rasters are walk_rect's: the memory-safety argument of srbh_raster_walk.h
+// carries over untouched; that of the bitmap and the tables is stated once, at zone_item_walk.  No global atomics, no host
 // synchronisation; per-item partials go to ws and a second kernel adds each zone's items in item order.
+#include "srbh_summary_select.h"
 #include "srbh_zone_bitmap.h"
 
 namespace {
@@ -39,70 +41,31 @@ struct ZAcc {
 template <int EV, int EM, bool HIST>
 __global__ __launch_bounds__(256) void zone_item_kernel(const SumParams p, const ZoneTables z, unsigned magic, int nbins, void* __restrict__ ws) {
     using G = Group<EV, EM>;
-    __shared__ unsigned bm[BM_WORDS + 1];                             // (+ 1: a group's bits are read as a pair of words)
+    __shared__ unsigned bm[BM_WORDS + 1];
     __shared__ unsigned hist[HIST ? VH_MAX_BINS : 1];
     const int t = threadIdx.x;
     const long item = blockIdx.x;                                     // < NI
-    const int* q = z.items + 5 * item;
-    const int zone = q[0];
-    const Rect w = clip_window(q + 1, p.r.H, p.r.W);
-    int e0 = 0, e1 = 0;
-    if (zone >= 0 && zone < z.Z) {
-        const int a = z.edge_off[zone], b = z.edge_off[zone + 1];
-        if (a >= 0 && a <= b && b <= z.E) { e0 = a; e1 = b; }
-    }
     if (HIST) {
-        for (int i = t; i < nbins; i += 256) hist[i] = 0u;
+        for (int i = t; i < nbins; i += 256) hist[i] = 0u;            // (a barrier follows before any lane counts: the walk's, or the one below)
     }
-    if (t == 0) bm[BM_WORDS] = 0u;
     ZAcc acc = {0, {0, 0u, 0ull, 0ull}};
     const unsigned last = (unsigned)nbins - 1u;
-    if (w.any && e1 > e0) {                                           // uniform
-        const int width = w.x1 - w.x0;
-        const int full = (int)(((long)width + 31) >> 5);
-        const int wpr = full < BM_MAX_WPR ? full : BM_MAX_WPR, segw = wpr * 32, rbmax = BM_WORDS / wpr;
-        for (long done = 0; done < w.rows; done += rbmax) {
-            const int yb = w.y0 + (int)done, left = w.rows - (int)done, rb = left < rbmax ? left : rbmax;
-            for (long xl = w.x0; xl < w.x1; xl += segw) {
-                const int xs = (int)xl, xe = xl + segw < w.x1 ? (int)(xl + segw) : w.x1;
-                __syncthreads();                                      // the walk before is done with bm
-                for (int i = t; i < rb * wpr; i += 256) bm[i] = 0u;
-                __syncthreads();
-                toggle_edges(z.edges, e0, e1, yb, rb, xs, xe, wpr, bm);
-                __syncthreads();
-                suffix_xor_rows(bm, rb, wpr);
-                __syncthreads();
-                walk_rect<EV, EM>(p.r, xs, xe, yb, rb, t, 256, [&](const G& g) {
-                    const int row = (int)(((unsigned long long)(g.rowA - p.r.a) >> z.row_tz) * z.row_inv) - yb;      // in [0, rb)
-                    const unsigned* brow = bm + row * wpr;
-                    const int off = g.c0 - xs;                        // in (-P, segw)
-                    unsigned zb;
-                    if (off >= 0) {
-                        const unsigned long long pair = brow[off >> 5] | ((unsigned long long)brow[(off >> 5) + 1] << 32);
-                        zb = (unsigned)(pair >> (off & 31));
-                    } else {
-                        zb = brow[0] << -off;
-                    }
-                    zb &= g.inside();                                 // (bits beyond xe belong to the next row or are the suffix's spill)
-                    if (!zb) return;
-                    unsigned wv[G::WORDS_A];
-                    const unsigned sel = select_group(p, g, wv) & zb;
-                    if (HIST) {
+    zone_item_walk<EV, EM>(p.r, z, item, bm, [&](const G& g, long, unsigned zb) {
+        unsigned wv[G::WORDS_A];
+        const unsigned sel = select_group(p, g, wv) & zb;
+        if (HIST) {
 #pragma unroll
-                        for (int j = 0; j < G::P; ++j) {
-                            if ((sel >> j) & 1u) {
-                                const unsigned v = group_pixel<EV>(wv, j), qv = magic ? __umulhi(v, magic) : v;
-                                atomicAdd(&hist[qv < last ? qv : last], 1u);
-                            }
-                        }
-                    } else {
-                        acc.cnt += __popc(zb);
-                        add_group<EV>(acc.a, sel, wv);
-                    }
-                });
+            for (int j = 0; j < G::P; ++j) {
+                if ((sel >> j) & 1u) {
+                    const unsigned v = group_pixel<EV>(wv, j), qv = magic ? __umulhi(v, magic) : v;
+                    atomicAdd(&hist[qv < last ? qv : last], 1u);
+                }
             }
+        } else {
+            acc.cnt += __popc(zb);
+            add_group<EV>(acc.a, sel, wv);
         }
-    }
+    });
     if (HIST) {
         __syncthreads();
         unsigned* o = (unsigned*)ws + item * nbins;
@@ -118,22 +81,6 @@ __global__ __launch_bounds__(256) void zone_item_kernel(const SumParams p, const
             o[4] = acc.a.mx;
         }
     }
-}
-
-// a lane per zone: its items' partials added in item order
-__global__ __launch_bounds__(256) void zone_sums_fold_kernel(const ZoneTables z, const long long* __restrict__ ws, long long* __restrict__ out) {
-    const long zone = blockIdx.x * 256L + threadIdx.x;
-    if (zone >= z.Z) return;
-    int i0, i1;
-    zone_items(z, (int)zone, &i0, &i1);
-    long long s[5] = {0, 0, 0, 0, 0};
-    for (int i = i0; i < i1; ++i) {
-        const long long* a = ws + 5 * (long)i;
-        s[0] += a[0]; s[1] += a[1]; s[2] += a[2]; s[3] += a[3];
-        s[4] = s[4] > a[4] ? s[4] : a[4];
-    }
-#pragma unroll
-    for (int k = 0; k < 5; ++k) out[5 * zone + k] = s[k];
 }
 
 // block (zone, 256 bins): a lane per bin
@@ -161,7 +108,7 @@ int zone_launch(const char* who, const void* v, int typeV, long rsV, const void*
     int rc = sum_params(who, v, typeV, rsV, m, typeM, rsM, H, W, vthr, mthr, &p);
     if (rc != SRBH_OK) return rc;
     ZoneTables z;
-    rc = zone_tables(who, edges, edge_off, Z, E, items, item_off, NI, p, typeV, &z);
+    rc = zone_tables(who, edges, edge_off, Z, E, items, item_off, NI, (unsigned long long)rsV * (unsigned)raster_esz(typeV), &z);
     if (rc != SRBH_OK) return rc;
     SRBH_REQUIRE((uintptr_t)ws % 8 == 0 && (uintptr_t)out % 8 == 0, "%s: out and ws must be aligned to 8 bytes", who);
     const unsigned magic = HIST ? vh_magic(bin_width) : 0u;
@@ -174,7 +121,7 @@ int zone_launch(const char* who, const void* v, int typeV, long rsV, const void*
     if (HIST)
         hipLaunchKernelGGL(zone_hist_fold_kernel, dim3((unsigned)Z, (unsigned)((nbins + 255) / 256)), dim3(256), 0, st, z, nbins, (const unsigned*)ws, out);
     else
-        hipLaunchKernelGGL(zone_sums_fold_kernel, dim3((unsigned)((Z + 255L) / 256)), dim3(256), 0, st, z, (const long long*)ws, out);
+        hipLaunchKernelGGL((zone_fold_kernel<5, 4>), dim3((unsigned)((Z + 255L) / 256)), dim3(256), 0, st, z, (const long long*)ws, out);
     SRBH_HIP(hipGetLastError());
     return SRBH_OK;
 }

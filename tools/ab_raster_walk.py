@@ -1,10 +1,13 @@
 #!/usr/bin/env python
-"""Two builds of libsrbh against each other on the city kernels (csrc/srbh_cells.hip, csrc/srbh_summary.hip): same integers, same speed.
+"""Two builds of libsrbh against each other on the city kernels: same integers, same speed.
 
-    python tools/ab_raster_walk.py --parent-lib /path/to/parent/libsrbh.so [--rounds 9] [--bits-out ...] [--bench-out ...]
+    python tools/ab_raster_walk.py --parent-lib /path/to/parent/libsrbh.so [--group rect|zones] [--rounds 9] [--bits-out ...] [--bench-out ...]
 
-Both libraries (one ABI) are loaded into ONE process; the Python layer of this tree drives either.  Workloads, rasters and method are
-those of tools/time_city_grid.py and tools/time_city_summary.py (their make_mask / make_pair / event_ms / rotating are imported).
+Both libraries (one ABI) are loaded into ONE process; the Python layer of this tree drives either.  Two groups of entries (--group; both
+by default): "rect", the rectangle kernels of csrc/srbh_cells.hip and csrc/srbh_summary.hip -- workloads, rasters and method of
+tools/time_city_grid.py and tools/time_city_summary.py (their make_mask / make_pair / event_ms / rotating are imported) --, and "zones",
+the zone and pair kernels of csrc/srbh_zones.hip, csrc/srbh_compare.hip and csrc/srbh_zone_compare.hip (zone_sums, zone_histogram,
+zone_pair_sums, pair_sums, class_sums) on tools/time_city_compare.py's triple and tools/time_city_zones.py's two zone sets.
   bits   every entry on every element-size pairing: sha256 of the result of either library, which must be equal;
   bench  HIP events around one call each, every side warmed up, buffers in rotation beyond the 256 MiB Infinity Cache, --rounds
          alternations (the side that goes first alternates too) of the tools' calls per side; per line the rounds' medians, their median
@@ -24,11 +27,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
+import time_city_compare as TC  # noqa: E402
 import time_city_grid as TG  # noqa: E402
 import time_city_summary as TS  # noqa: E402
+import time_city_zones as TZ  # noqa: E402
 from srbh_amd import _lib  # noqa: E402
+from srbh_amd import city_compare as CC  # noqa: E402
 from srbh_amd import city_grid as CG  # noqa: E402
 from srbh_amd import city_summary as CS  # noqa: E402
+from srbh_amd import city_zone_compare as CZC  # noqa: E402
+from srbh_amd import city_zones as CZ  # noqa: E402
 
 DEV = "cuda:0"
 LIBS = {}
@@ -53,6 +61,8 @@ def digest(t):
     if isinstance(t, dict):
         t = np.concatenate([np.asarray([t["count"], t["n"], t["max"]], dtype=np.int64), t["hist"], t["class_counts"],
                             np.asarray([t["mean"], t["std"]], dtype=np.float64).view(np.int64)])
+    elif isinstance(t, tuple):                                          # (class_sums: the rows and bad)
+        t = torch.cat([x.reshape(-1) for x in t]).cpu().numpy()
     else:
         t = t.cpu().numpy()
     return hashlib.sha256(np.ascontiguousarray(t).tobytes()).hexdigest()[:16]
@@ -67,13 +77,54 @@ def as_dtype(t, dtype):
     return (t.view(torch.int16) >> 3).to(torch.uint8)
 
 
-def bits(rows):
-    def both(name, fn, *a):
-        d = {side: digest(on(side, fn)(*a)) for side in ("parent", "tree")}
-        rows.append("%-72s %s %s %s" % (name, d["parent"], d["tree"], "equal" if d["parent"] == d["tree"] else "DIFFERENT"))
-        print(rows[-1], flush=True)
-        return d["parent"] == d["tree"]
+def both(rows, name, fn, *a):
+    d = {side: digest(on(side, fn)(*a)) for side in ("parent", "tree")}
+    rows.append("%-72s %s %s %s" % (name, d["parent"], d["tree"], "equal" if d["parent"] == d["tree"] else "DIFFERENT"))
+    print(rows[-1], flush=True)
+    return d["parent"] == d["tree"]
 
+
+def zone_workloads():
+    """-> [(tag, Zones)] of tools/time_city_zones.py's two sets, and time_city_compare's fishnet as device windows"""
+    one, many = TZ.zone_sets()
+    pos_d = torch.from_numpy(CG.fishgrid_windows(TC.W, TC.H, 256, 224).astype(np.int32)).to(DEV)
+    return [("one zone of 1000 vertices", CZ.zone_edges(one)), ("301 zones", CZ.zone_edges(many))], pos_d
+
+
+def bits_zones(rows):
+    ok = True
+    h16, r16, b8 = TC.make_triple(torch.Generator(device=DEV).manual_seed(23))
+    sets, pos_d = zone_workloads()
+    for tv in (torch.uint16, torch.uint8):
+        for tm in (None, torch.uint8, torch.uint16):
+            v, m = as_dtype(h16, tv), None if tm is None else as_dtype(b8, tm)
+            for ztag, zones in sets:
+                tag = "%s / %s, %s" % (tv, tm, ztag)
+                ok &= both(rows, "zone_sums %s" % tag, CZ.zone_sums, v, zones, m)
+                ok &= both(rows, "zone_histogram %s, 10, 256" % tag, CZ.zone_histogram, v, zones, 10, 256, m)
+            for tr in (torch.uint16, torch.uint8):
+                r = as_dtype(r16, tr)
+                tag = "%s / %s / %s" % (tv, tr, tm)
+                for ztag, zones in sets:
+                    ok &= both(rows, "zone_pair_sums %s, %s" % (tag, ztag), CZC.zone_pair_sums, v, r, zones, m)
+                ok &= both(rows, "pair_sums %s, %d windows" % (tag, len(pos_d)), CC.pair_sums, v, r, pos_d, m)
+                ok &= both(rows, "class_sums %s, C = %d" % (tag, TC.C), CC.class_sums, v, r, TC.EDGES, m)
+                del r
+            del v, m
+    return ok
+
+
+def bits(rows, groups):
+    ok = True
+    if "rect" in groups:
+        ok &= bits_rect(rows)
+    if "zones" in groups:
+        ok &= bits_zones(rows)
+    rows.append("ALL EQUAL" if ok else "SOME DIFFER")
+    return ok
+
+
+def bits_rect(rows):
     ok = True
     g = torch.Generator(device=DEV).manual_seed(20)
     for H, W in ((3000, 4000), (7900, 7900)):
@@ -83,9 +134,9 @@ def bits(rows):
         for ta in (torch.uint8, torch.uint16):
             for tb in (None, torch.uint8, torch.uint16):
                 a, b = as_dtype(m8, ta), None if tb is None else as_dtype(o8, tb)
-                ok &= both("cell_counts %d x %d %s / %s, %d windows" % (H, W, ta, tb, len(pos_d)), CG.cell_counts, a, pos_d, b)
+                ok &= both(rows, "cell_counts %d x %d %s / %s, %d windows" % (H, W, ta, tb, len(pos_d)), CG.cell_counts, a, pos_d, b)
         a, b = as_dtype(m8, torch.uint16).view(torch.int16), as_dtype(o8, torch.uint16).view(torch.int16)
-        ok &= both("cell_counts %d x %d int16 / int16, the value itself, threshold -1" % (H, W), lambda: CG.cell_counts(a, pos_d, b, -1, False))
+        ok &= both(rows, "cell_counts %d x %d int16 / int16, the value itself, threshold -1" % (H, W), lambda: CG.cell_counts(a, pos_d, b, -1, False))
     del m8, o8, a, b
     g = torch.Generator(device=DEV).manual_seed(21)
     h16, b8 = TS.make_pair(g)
@@ -95,13 +146,12 @@ def bits(rows):
         for tm in (None, torch.uint8, torch.uint16):
             v, m = as_dtype(h16, tv), None if tm is None else as_dtype(b8, tm)
             tag = "%d x %d %s / %s" % (H, W, tv, tm)
-            ok &= both("window_sums %s, %d windows" % (tag, len(pos_d)), CS.window_sums, v, pos_d, m)
+            ok &= both(rows, "window_sums %s, %d windows" % (tag, len(pos_d)), CS.window_sums, v, pos_d, m)
             for block in (4, 40, 400):
-                ok &= both("block_sums %s, block %d" % (tag, block), CS.block_sums, v, block, m)
-            ok &= both("value_histogram %s, 10, 256" % tag, CS.value_histogram, v, 10, 256, m)
+                ok &= both(rows, "block_sums %s, block %d" % (tag, block), CS.block_sums, v, block, m)
+            ok &= both(rows, "value_histogram %s, 10, 256" % tag, CS.value_histogram, v, 10, 256, m)
             del v, m
-    ok &= both("city_summary %d x %d uint16 / uint8" % (H, W), CS.city_summary, h16, b8)
-    rows.append("ALL EQUAL" if ok else "SOME DIFFER")
+    ok &= both(rows, "city_summary %d x %d uint16 / uint8" % (H, W), CS.city_summary, h16, b8)
     return ok
 
 
@@ -127,7 +177,44 @@ def bench_line(rows, name, fn, bufs, calls, rounds):
     return ok
 
 
-def bench(rows, rounds):
+def bench_zones(rows, rounds):
+    ok = True
+    g = torch.Generator(device=DEV).manual_seed(23)
+    triples = [TC.make_triple(g) for _ in range(2)]
+    assert len(triples) * TC.H * TC.W * 5 > TC.L3_BYTES
+    small = [(as_dtype(h, torch.uint8), as_dtype(r, torch.uint8), b) for h, r, b in triples]      # the forms with 16 pixels to a group
+    sets, pos_d = zone_workloads()
+    lib = _lib.lib()
+    cws = torch.empty(lib.srbh_pair_class_ws_bytes(TC.H, TC.W, TC.C), dtype=torch.uint8, device=DEV)
+    for ztag, zones in sets:
+        NI = len(CZ.zone_items(zones, TC.H, TC.W)[0])
+        ws = torch.empty(max(lib.srbh_zone_hist_ws_bytes(NI, 256), lib.srbh_zone_pair_ws_bytes(NI)), dtype=torch.uint8, device=DEV)
+        for ttag, bufs in (("uint16 height and reference, uint8 class", triples), ("uint8 height and reference, uint8 class", small)):
+            tag = "%s, %d items, %s" % (ztag, NI, ttag)
+            ok &= bench_line(rows, "zone_sums(height, zones, build), " + tag, lambda h, r, b: CZ.zone_sums(h, zones, b, workspace=ws), bufs, 6, rounds)
+            ok &= bench_line(rows, "zone_histogram(height, zones, 10, 256, build), " + tag,
+                             lambda h, r, b: CZ.zone_histogram(h, zones, 10, 256, b, workspace=ws), bufs, 6, rounds)
+            ok &= bench_line(rows, "zone_pair_sums(height, ref, zones, build), " + tag,
+                             lambda h, r, b: CZC.zone_pair_sums(h, r, zones, b, workspace=ws), bufs, 6, rounds)
+    for ttag, bufs in (("uint16 height and reference, uint8 class", triples), ("uint8 height and reference, uint8 class", small)):
+        ok &= bench_line(rows, "pair_sums(height, ref, %d windows of 256 / 224, build), %s" % (len(pos_d), ttag),
+                         lambda h, r, b: CC.pair_sums(h, r, pos_d, b), bufs, 6, rounds)
+        ok &= bench_line(rows, "class_sums(height, ref, edges, build), C = %d, %s" % (TC.C, ttag),
+                         lambda h, r, b: CC.class_sums(h, r, TC.EDGES, b, workspace=cws), bufs, 6, rounds)
+    return ok
+
+
+def bench(rows, rounds, groups):
+    ok = True
+    if "rect" in groups:
+        ok &= bench_rect(rows, rounds)
+    if "zones" in groups:
+        ok &= bench_zones(rows, rounds)
+    rows.append("ALL PASS" if ok else "SOME FAIL")
+    return ok
+
+
+def bench_rect(rows, rounds):
     ok = True
     g = torch.Generator(device=DEV).manual_seed(20)
     for H, W, nmasks in ((3000, 4000, 24), (7900, 7900, 5)):
@@ -156,7 +243,6 @@ def bench(rows, rounds):
         ok &= bench_line(rows, "block_sums, block %d, %s" % (block, tag), lambda h, b: CS.block_sums(h, block, b), pairs, 6, rounds)
     ok &= bench_line(rows, "value_histogram(height, 10, 256, build), " + tag, lambda h, b: CS.value_histogram(h, 10, 256, b, workspace=ws), pairs, 6, rounds)
     ok &= bench_line(rows, "city_summary(height, build) whole, host time included, " + tag, CS.city_summary, pairs, 6, rounds)
-    rows.append("ALL PASS" if ok else "SOME FAIL")
     return ok
 
 
@@ -167,6 +253,7 @@ def main():
     ap.add_argument("--bits-out", default=os.path.join(ROOT, "profiles", "raster_walk_bits.txt"))
     ap.add_argument("--bench-out", default=os.path.join(ROOT, "profiles", "raster_walk_bench.txt"))
     ap.add_argument("--only", choices=["bits", "bench"], default=None)
+    ap.add_argument("--group", choices=["rect", "zones"], default=None, help="one group of entries (default: both)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "this is a measurement: it needs the GPU"
     LIBS["parent"], LIBS["tree"] = load(args.parent_lib), load(_lib.LIB_PATH)
@@ -180,7 +267,8 @@ def main():
                              "ms per call, medians of the tools' calls per round; " % args.rounds + dev)):
         if args.only in (None, part):
             rows = [head, ""]
-            ok &= (bits if part == "bits" else lambda r: bench(r, args.rounds))(rows)
+            groups = (args.group,) if args.group else ("rect", "zones")
+            ok &= bits(rows, groups) if part == "bits" else bench(rows, args.rounds, groups)
             os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
             with open(out, "w") as fh:
                 fh.write("\n".join(rows) + "\n")

@@ -83,16 +83,7 @@ def main():
     triples = [TC.make_triple(g) for _ in range(2)]
     assert len(triples) * H * W * 5 > TS.L3_BYTES
     zeros = float((triples[0][1].view(torch.int16) == 0).double().mean())
-    rs = np.random.RandomState(7)
-    a = 2 * np.pi * np.arange(1000) / 1000
-    rad = 1 + 0.05 * np.sin(9 * a)
-    one = [[np.stack([W / 2 + 0.4 * W * rad * np.cos(a), H / 2 + 0.4 * H * rad * np.sin(a)], axis=1)]]
-    many = []
-    for k in range(301):
-        cx, cy = (k % 21 + 0.5) * (W / 21), (k // 21 + 0.5) * (H / 15)
-        b = np.sort(rs.uniform(0, 2 * np.pi, size=24))
-        r = 170 * rs.uniform(0.7, 1.0, size=24)
-        many.append([np.stack([cx + r * np.cos(b), cy + r * np.sin(b)], axis=1)])
+    one, many = TZ.zone_sets()
     rows, nprinted, tables = ["reference raster: %.1f %% zeros" % (100 * zeros), ""], 0, {}
     for tag, polys, calls in (("1. one zone of 1000 vertices over about half the raster", one, args.calls),
                               ("2. 301 zones of about 300 x 300 pixels", many, args.loop_calls)):

@@ -66,6 +66,21 @@ def boxes(zones):
     return np.array(out, dtype=np.int64)
 
 
+def zone_sets():
+    """the polygons of workloads 1 and 2 -> (one, many)"""
+    rs = np.random.RandomState(7)
+    a = 2 * np.pi * np.arange(1000) / 1000
+    rad = 1 + 0.05 * np.sin(9 * a)
+    one = [[np.stack([W / 2 + 0.4 * W * rad * np.cos(a), H / 2 + 0.4 * H * rad * np.sin(a)], axis=1)]]
+    many = []
+    for k in range(301):
+        cx, cy = (k % 21 + 0.5) * (W / 21), (k // 21 + 0.5) * (H / 15)
+        b = np.sort(rs.uniform(0, 2 * np.pi, size=24))
+        r = 170 * rs.uniform(0.7, 1.0, size=24)
+        many.append([np.stack([cx + r * np.cos(b), cy + r * np.sin(b)], axis=1)])
+    return one, many
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "city_zones_bench.txt"))
@@ -77,16 +92,7 @@ def main():
     g = torch.Generator(device=DEV).manual_seed(21)
     pairs = [TS.make_pair(g) for _ in range(2)]
     assert len(pairs) * H * W * 3 > TS.L3_BYTES
-    rs = np.random.RandomState(7)
-    a = 2 * np.pi * np.arange(1000) / 1000
-    rad = 1 + 0.05 * np.sin(9 * a)
-    one = [[np.stack([W / 2 + 0.4 * W * rad * np.cos(a), H / 2 + 0.4 * H * rad * np.sin(a)], axis=1)]]
-    many = []
-    for k in range(301):
-        cx, cy = (k % 21 + 0.5) * (W / 21), (k // 21 + 0.5) * (H / 15)
-        b = np.sort(rs.uniform(0, 2 * np.pi, size=24))
-        r = 170 * rs.uniform(0.7, 1.0, size=24)
-        many.append([np.stack([cx + r * np.cos(b), cy + r * np.sin(b)], axis=1)])
+    one, many = zone_sets()
     rows, nprinted = [], 0
     tables = {}
     for tag, polys, calls in (("1. one zone of 1000 vertices over about half the raster", one, args.calls),
