@@ -1137,6 +1137,62 @@ int srbh_zone_pair_sums(const void* p, int typeP, long row_strideP, const void* 
                         long row_strideM, int H, int W, const int* edges, const int* edge_off, int Z, int E, const int* items,
                         const int* item_off, int NI, int mode, int pthr, int rthr, int mthr, long long* out, void* ws, void* stream);
 
+/* ---- City labels: building footprints burned into a raster (the reference's shp_to_tiff / shp2tif, demo_preprocess_height_v2.py:27-119
+ * and main_shp2tif: one gdal.RasterizeLayer(..., options=["ATTRIBUTE=<field>"]) that paints every footprint, in feature order, with its
+ * attribute value -- the reference height raster of the validation entries above and the training labels; csrc/srbh_burn.hip) -----------
+ * out: a raster of logical shape (H, W), element type SRBH_GRID_U16 or SRBH_GRID_U8, WRITTEN in place through its ROW stride in ELEMENTS
+ * (>= W; the column stride is 1), aligned to its element size only: an interior view of a larger raster works.
+ *
+ * The rule (this project's own, like the zone rule above; no result of GDAL is compared).  Feature f of Z is a zone in the sense of the
+ * zone rule: all edges of all its rings, int32 fixed point with 8 fractional bits, |X|, |Y| <= 2^29, even-odd over its OWN edges, the pixel
+ * centre (x + 1/2, y + 1/2) decides, a centre on a left or top boundary is in, on a right or bottom boundary out.  Each feature has one
+ * value values[f], 0..65535 (0..255 for a uint8 raster; the kernel takes the low 16 / 8 bits).
+ *   merge = SRBH_BURN_LAST (GDAL's replace): out[y][x] = values[f] of the LARGEST f whose zone holds the pixel.  A value of 0 burns like
+ *                          any other.
+ *   merge = SRBH_BURN_MAX:  the largest value among the features whose zones hold the pixel: independent of the order.
+ * A pixel in no feature gets init; with keep != 0 it is not written at all and out keeps its contents there.  Overlap between two
+ * features is resolved by merge; overlap of two parts of ONE feature is outside, as even-odd has always said.  Integers only: bit-equal
+ * between runs and independent of how the host cuts the work.
+ *
+ * Tables, int32 on the device:
+ *   edges, edge_off     exactly srbh_zone_sums' tables (the same uploaded tables serve both); edges aligned to 16 bytes; an edge with a
+ *                       coordinate beyond +-2^29 contributes nothing; an edge range outside [0, E] is an empty feature
+ *   values   [Z]        the value of each feature
+ *   boxes    [Z][4]     (x0, y0, x1, y1), half open, in pixels: the rows y with Ymin <= 256 y + 128 < Ymax and the columns floor(Xmin / 256)
+ *                       .. ceil(Xmax / 256) of the feature's edges, clipped to the raster (city_zones.zone_items' rows and columns).  Only
+ *                       a filter: a wave skips a feature whose box misses its rectangle; a box that is too small loses pixels, one that
+ *                       is too large costs time
+ *   tile_off [NT + 1]   the raster is cut into tiles of srbh_burn_tile() = 64 x 64 pixels anchored at pixel (0, 0), NT = ceil(H / 64) *
+ *                       ceil(W / 64) in row-major tile order; tile t walks tile_feat[tile_off[t] .. tile_off[t + 1]); a range outside
+ *                       [0, NF] is an empty tile
+ *   tile_feat [NF]      feature indices, ASCENDING within a tile (the order is the rule of SRBH_BURN_LAST); every feature whose box meets
+ *                       the tile must be listed (city_burn.burn_tiles cuts them); an index outside [0, Z) does nothing.  NF = 0 is legal:
+ *                       every tile is then empty (tile_feat must still be a valid pointer)
+ * One workgroup of 256 lanes per tile, the grid is every tile of the raster; a tile without features stores init, or nothing under keep.
+ * A wave owns 16 rows x 64 columns, a lane 16 consecutive pixels of one row, and the lane's values live in registers from the first
+ * feature to the store: no LDS, no barrier, no atomic of any kind.  Per feature the box is tested against the wave's rectangle, per edge
+ * its row range and right extent (both uniform across the wave); then each lane runs the crossing test for its row -- oriented so that
+ * den = Y1 - Y0 > 0, with N as in the zone rule, pixel x is toggled iff cx den < N, cx = 256 x + 128; for the lane's run of 16 pixels that
+ * is four compares of R = N - cx0 den against 8, 4, 2 and 1 times 256 den -- and XORs a 16-bit mask into its parity; after the feature's
+ * last edge the lane replaces (or maxes) its values under the parity.  Overflow: |N| < 2^61 as in the zone rule; cx den stays inside int64
+ * only because a pixel with cx > 2^29 cannot lie in any zone: the columns x >= 2^21 never burn, and a tile there walks no feature before
+ * any product is formed, so |X0 - cx0| <= 2^30 and |R| < 2^61.
+ * Stores: a lane's 16 pixels go out as aligned 16-byte vector stores when the run lies wholly inside the raster and its address is
+ * 16-byte aligned (and, under keep, all 16 were burned), otherwise element by element, each store predicated on x < W && y < H.  No byte
+ * outside out's rows [0, H) x [0, W) is written, whatever the tables hold: wrong tables give wrong pixels at worst, never a load outside
+ * the tables' own bytes nor a store outside out.  No host synchronisation.
+ *
+ * Refused with SRBH_ERR_ARG, nothing launched, nothing written: a null out or table; a type other than SRBH_GRID_U16 / SRBH_GRID_U8; H, W,
+ * Z or E <= 0, or NF < 0; H * W >= 2^31; a row stride below W; out not aligned to its element size; edges not aligned to 16 bytes, another
+ * table not to 4; NT not equal to the tile count of H x W; merge outside 0..1; init outside the type's range. */
+#define SRBH_BURN_LAST 0
+#define SRBH_BURN_MAX 1
+int srbh_burn_tile(void);    /* 64: the tile side the tables must be cut for; host only */
+int srbh_burn(void* out, int typeO, long row_strideO, int H, int W,
+              const int* edges, const int* edge_off, const int* values, const int* boxes, int Z, int E,
+              const int* tile_off, const int* tile_feat, int NT, int NF,
+              int merge, int keep, int init, void* stream);
+
 /* ---- The middle of an MBConv block in ONE launch per direction (round 4; efficientnet_pytorch MBConvBlock.forward between the expand and
  * the project conv, run by smp's encoder at mymodels.py:276): BatchNorm0 (training) + SiLU -> depthwise KxK, stride 1, "same" zero padding ->
  * BatchNorm1 (training) + SiLU (+ the plane means squeeze-and-excitation pools).  fp32 NCHW, square planes 2x2 / 4x4 / 8x8, K = 3 | 5.

@@ -17,7 +17,7 @@ CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(ROOT, "include")
 LIB_PATH = os.path.join(_HERE, "libsrbh.so")
 _DEV_LIB = os.environ.get("SRBH_LIB_PATH")      # developer A/B only (tools/ab_variants.sh): load another build of the same ABI
-SOURCES = ["srbh_conv3x3.hip", "srbh_aux.hip", "srbh_rrdbnet.hip", "srbh_ptrunk.hip", "srbh_trunk_wgrad.hip", "srbh_ptail.hip", "srbh_ptail_split.hip", "srbh_head.hip", "srbh_head_bwd.hip", "srbh_mosaic.hip", "srbh_loader.hip", "srbh_loss.hip", "srbh_sr_metrics.hip", "srbh_eval.hip", "srbh_stats.hip", "srbh_cells.hip", "srbh_summary.hip", "srbh_zones.hip", "srbh_compare.hip", "srbh_zone_compare.hip", "srbh_dwconv.hip", "srbh_enc_eval.hip", "srbh_mbconv.hip", "srbh_pwconv.hip", "srbh_dconv.hip", "srbh_optim.hip", "srbh_vgg.hip", "srbh_disc.hip", "srbh_disc3.hip"]
+SOURCES = ["srbh_conv3x3.hip", "srbh_aux.hip", "srbh_rrdbnet.hip", "srbh_ptrunk.hip", "srbh_trunk_wgrad.hip", "srbh_ptail.hip", "srbh_ptail_split.hip", "srbh_head.hip", "srbh_head_bwd.hip", "srbh_mosaic.hip", "srbh_loader.hip", "srbh_loss.hip", "srbh_sr_metrics.hip", "srbh_eval.hip", "srbh_stats.hip", "srbh_cells.hip", "srbh_summary.hip", "srbh_zones.hip", "srbh_compare.hip", "srbh_zone_compare.hip", "srbh_burn.hip", "srbh_dwconv.hip", "srbh_enc_eval.hip", "srbh_mbconv.hip", "srbh_pwconv.hip", "srbh_dconv.hip", "srbh_optim.hip", "srbh_vgg.hip", "srbh_disc.hip", "srbh_disc3.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # NOTE: `-mllvm -amdgpu-mfma-vgpr-form=1` (accumulators in VGPRs: no v_accvgpr copies at K-loop back-edges).  Round 1 saw the
 # first persistent trunk kernel produce non-deterministic garbage with it; round 3 re-ran it on the current kernel (ptrunk3:
@@ -390,6 +390,8 @@ SIGNATURES = {
     "srbh_zone_pair_ws_bytes": (_sz, [_i]),
     "srbh_zone_pair_sums": (_i, [_vp, _i, C.c_long, _vp, _i, C.c_long, _vp, _i, C.c_long, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i,
                                  _vp, _vp, _vp]),
+    "srbh_burn_tile": (_i, []),
+    "srbh_burn": (_i, [_vp, _i, C.c_long, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "srbh_wconv3x3": (_i, [C.POINTER(WConvArgs), _vp]),
     "srbh_vgg_input_f16": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),
     "srbh_vgg_relu_pool_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),

@@ -20,8 +20,8 @@ ALL_TOUCHED on the value raster's own grid; no result of GDAL is compared, and t
 grid (anchored at the polygon's own xmin, ymax) is not reproduced.
 
 A pixel is SELECTED as in city_summary -- inside the raster, ``value > value_threshold`` and (no mask or ``mask > mask_threshold``) --
-and in the zone.  Raster units throughout.  GPU only.  Reading shapefiles, reprojection, GeoTIFFs, the .xls and a burned label raster
-are out of scope."""
+and in the zone.  Raster units throughout.  GPU only.  Reading shapefiles, reprojection, GeoTIFFs and the .xls are out of scope; a
+burned label raster is ``city_burn``'s."""
 import numpy as np
 import torch
 
